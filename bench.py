@@ -12,10 +12,17 @@ emission, tree reuse and game recycling.  Everything runs on the GPU with states
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
     python bench.py [--gpus N] --train                     (config C5 alone: the data-parallel training step)
+    python bench.py ... --full                             (everything beside the headline, see below)
+    python bench.py ... --dump-outputs DIR                 (the last timed ply's results as DIR/<name>.npy, see dump_outputs)
+
+A plain run measures the headline alone: set-up, W warm-up plies, K timed plies (with the tower's roofline sampled inside
+them), the JSON line.  --full adds what takes runs of its own: the split-bf16 run and its measured deviation
+(`alt_precision`), the extra configurations (`extra`: 120 sustained plies, 4x the games, C3, the reference's constants),
+config C5 (`extra.train_c5`) and the CPU baseline (`cpu_baseline`); the --no-* options leave out parts of it.
 
 Self-play shards by game with no data-path collective: rank r owns games
 [r·4096, (r+1)·4096) with their own RNG streams; RCCL is used only for the barrier / max-over-ranks
-timing.  Config C5 (`extra.train_c5`, every N): the 10-block x 128-filter network plays, then trains on its own
+timing.  Config C5 (`extra.train_c5` with --full, every N): the 10-block x 128-filter network plays, then trains on its own
 examples with the reference's chunking (500 examples x 8 symmetries, 20 chunks per optimiser step,
 alpha-tak/src/model/network.rs:89-96); with N > 1 every step all-reduces the 32.3 MB flat gradient buffer over RCCL
 inside libtakgpu — the only collective of the build.  Rank 0 prints ONE JSON line.
@@ -489,6 +496,66 @@ def eng_param_bytes(blocks, filters, n):
     return 4 * p
 
 
+DUMP_BUDGET = 64 << 20    # bytes of all --dump-outputs files of one run together (all ranks)
+DUMP_MAX_EXAMPLES = 1 << 16  # finished examples fetched from the ring at most (the first ones, in drain order)
+DUMP_SEED = 12345         # the fixed sample of games / examples written when a group exceeds its share of the budget
+
+
+def dump_outputs(eng, out_dir, rank=0, world=1):
+    """--dump-outputs: what the self-play driver hands its caller after the last timed ply, as DIR/<name>.npy (float32; float64
+    where an integer may exceed 24 bits).  Per game (tg_search_states / tg_search_root): the root state after the ply's move
+    (packed state bytes) and the reused root's children — move codes, visits, priors, Q — with its visit count and value.
+    The finished examples in the ring (tg_selfplay_drain: game id, result, state, moves, visits) and the driver's counters
+    (tg_selfplay_stats, one stat_<name>.npy each).  Move columns past the widest list are dropped.  A group (games, examples)
+    larger than half the budget is written as a fixed seeded sample of its rows, their indices in <group>_rows.npy.  With
+    N > 1 ranks, rank r writes its own games as rank<r>_<name>.npy within 1/N of the budget.  → bytes written"""
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    stats = eng.selfplay_stats()
+    root = eng.search_root()
+    k = max(int(root["counts"].max()), 1)
+    games = {
+        "root_states": eng.search_states().astype(np.float32),
+        "root_moves": root["moves"][:, :k].astype(np.float32),
+        "root_child_visits": root["visits"][:, :k].astype(np.float64),
+        "root_prior": root["prior"][:, :k].astype(np.float32),
+        "root_q": root["q"][:, :k].astype(np.float32),
+        "root_counts": root["counts"].astype(np.float64),
+        "root_visits": root["root_visits"].astype(np.float64),
+        "root_value": root["root_q"].astype(np.float32),
+    }
+    hdr, states, moves, visits = eng.selfplay_drain(max(1, min(int(stats["examples"]), DUMP_MAX_EXAMPLES)))
+    k = max(int(hdr["n_moves"].max()), 1) if len(hdr) else 1
+    examples = {
+        "example_game_id": hdr["game_id"].astype(np.float64),
+        "example_n_moves": hdr["n_moves"].astype(np.float64),
+        "example_result": hdr["result"].astype(np.float32),
+        "example_states": states.astype(np.float32),
+        "example_moves": moves[:, :k].astype(np.float32),
+        "example_visits": visits[:, :k].astype(np.float64),
+    }
+    share = (DUMP_BUDGET // world - (1 << 16)) // 2  # (64 KB for the .npy headers and the counters)
+
+    def fit(group, name):
+        rows = len(next(iter(group.values())))
+        per_row = sum(a.nbytes for a in group.values()) / max(rows, 1) + 8
+        keep = min(rows, int(share // per_row))
+        if keep == rows:
+            return group
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))
+        return dict({n: a[idx] for n, a in group.items()}, **{name + "_rows": idx.astype(np.float64)})
+
+    arrays = {**fit(games, "root"), **fit(examples, "example")}
+    arrays.update({"stat_" + n: np.array([v], np.float64) for n, v in stats.items()})
+    total = 0
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a))
+        total += a.nbytes
+    print(f"bench.py: rank {rank}: wrote {len(arrays)} arrays ({total / 2**20:.1f} MB) to {out_dir}", file=sys.stderr, flush=True)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -502,19 +569,25 @@ def main():
     ap.add_argument("--head", default="fc5", choices=["fc5", "conv"])
     ap.add_argument("--arena", type=int, default=0,
                     help="average MCTS node budget per game (all trees share one pool); 0 = sized by the engine from the free device memory")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: alt_precision, extra (C3, 4x games, 120 sustained plies, the "
+                         "reference's constants), extra.train_c5 and cpu_baseline; a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed plies, write what the last one left (root states and statistics, examples, counters) "
+                         "as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra lines of the JSON (config C3, 16 384 games, the 120-ply sustained run)")
+                    help="with --full: skip the extra lines of the JSON (config C3, 16 384 games, the 120-ply sustained run)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--cpu-games", type=int, default=256)
     ap.add_argument("--cpu-threads", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16x3"],
                     help="tower arithmetic: exact f32 MFMA (default, the parity path) or split-bf16 (3 bf16 MFMAs per product)")
-    ap.add_argument("--no-alt-precision", action="store_true", help="skip the second run on the bf16x3 path")
+    ap.add_argument("--no-alt-precision", action="store_true", help="with --full: skip the second run on the bf16x3 path")
     ap.add_argument("--profile-every", type=int, default=8, help="time the tower convs of every k-th forward (0 = off)")
     ap.add_argument("--train", action="store_true",
                     help="report config C5 alone (data-parallel training step on the 10x128 network) as the JSON line")
-    ap.add_argument("--no-train", action="store_true", help="skip extra.train_c5")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip extra.train_c5")
     ap.add_argument("--train-steps", type=int, default=2, help="optimiser steps timed (each = chunks-in-step chunks)")
     ap.add_argument("--train-chunk", type=int, default=500, help="examples per chunk (CHUNK_SIZE, network.rs:17)")
     ap.add_argument("--train-chunks-in-step", type=int, default=20, help="chunks per optimiser step (CHUNKS_IN_STEP, network.rs:18)")
@@ -535,6 +608,8 @@ def main():
                     help="with --rehearse-launch: this rank raises BEHIND the agreement, while the others wait in the rehearsed collective "
                          "(rank 0 must learn it from the store, print its line and every rank must leave, non-zero, long before the watchdog)")
     args = ap.parse_args()
+    if args.dump_outputs and args.train:
+        ap.error("--dump-outputs writes the self-play plies' results; --train times the training step instead")
 
     from tak_amd import dist as tdist
 
@@ -633,10 +708,11 @@ def main():
         if dist is not None:
             dist.barrier()
 
-    def run(precision, profile_every, cfg=None, steps=None, warmup=None, drain_every=0, rollouts=None):
+    def run(precision, profile_every, cfg=None, steps=None, warmup=None, drain_every=0, rollouts=None, dump_dir=None):
         """W untimed + K timed plies of self-play on a fresh engine → (seconds, expansions, evals, profile).  cfg =
         (board, blocks, filters, head, games, weights) overrides the command line (the extra lines); drain_every > 0
-        fetches the finished examples every so many plies inside the timed region, as a training loop would."""
+        fetches the finished examples every so many plies inside the timed region, as a training loop would; dump_dir:
+        after the timed region, dump_outputs writes what the last ply left there."""
         board, blocks, filters, head, games, weights = cfg or (args.board, args.blocks, args.filters, args.head, args.games, tensors)
         steps = args.steps if steps is None else steps
         warmup = args.warmup if warmup is None else warmup
@@ -670,13 +746,15 @@ def main():
         if profile_every:
             eng.profile_enable(0)
         s1 = eng.selfplay_stats()
+        if dump_dir:
+            dump_outputs(eng, dump_dir, rank, world)
         eng.close()
         run.last = {"games_finished": s1["games_finished"], "examples": s1["examples"], "drained": drained, "dropped_examples": s1["dropped_examples"]}
         return dt_local, s1["expansions"] - s0["expansions"], s1["evals"] - s0["evals"], prof
 
     out = None
     if not args.train:
-        dt_local, expansions, evals, prof = run(args.precision, args.profile_every)
+        dt_local, expansions, evals, prof = run(args.precision, args.profile_every, dump_dir=args.dump_outputs)
         dt, total_exp = tdist.reduce_time_and_count(dist, dt_local, expansions, device="cuda" if backend == "nccl" else "cpu")
         reporting = tdist.ranks_reporting(dist, device="cuda" if backend == "nccl" else "cpu")
         by_rank = tdist.per_rank_times(dist, dt_local / max(args.steps, 1))
@@ -736,7 +814,7 @@ def main():
                     "frac_executed": prof.get("conv_flops_executed", prof["conv_flops"]) / (avg_ms * 1e-3) / 1e12 / peak,
                     "forward_ms": prof["forward_ms"] / max(prof["forwards"], 1),
                 }
-            if world == 1 and args.precision == "f32" and not args.no_alt_precision and tak_amd_supports_bf16x3(args):
+            if args.full and world == 1 and args.precision == "f32" and not args.no_alt_precision and tak_amd_supports_bf16x3(args):
                 # the same workload on the split-bf16 tower / policy FC (3 bf16 MFMAs per product, f32 accumulate): measured
                 # deviation from the f32 forward ≤ 1.1e-5 relative on the policy, ≤ 5e-6 on the eval (tests/test_gpu_net.py),
                 # inside the 1e-4 of the reference comparison; trees differ from the f32 run only through those last bits
@@ -752,7 +830,7 @@ def main():
                     out["alt_precision"] = alt
                 except Exception as ex:
                     out["alt_precision"] = {"error": repr(ex)}
-            if world == 1 and args.precision == "f32" and not args.no_extras:
+            if args.full and world == 1 and args.precision == "f32" and not args.no_extras:
                 # more lines than the headline, same engine, same timing discipline (fresh engine, warm-up ply, sync on both sides):
                 # the other single-GPU BASELINE config, the north star's "≥ 10 k concurrent games", and a long run with drains
                 extras = {}
@@ -792,7 +870,7 @@ def main():
                 out["extra"] = extras
     # config C5 on every rank (the only part of the bench with a data-path collective)
     c5_failed = False
-    if args.train or not (args.no_train or args.no_extras or args.precision != "f32"):
+    if args.train or (args.full and not (args.no_train or args.no_extras or args.precision != "f32")):
         out, c5_failed, c5 = run_c5_phase(args, rank, world, out, lambda progress: train_c5(args, rank, world, local_rank, dist, backend, barrier, progress), want_result=True, dist=dist)
         if rank == 0 and args.train and (c5_failed or "error" in c5):
             out = failed_train_line(world, c5.get("error"))
@@ -810,7 +888,7 @@ def main():
                 "train_c5": c5,
             }
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1 and not args.train:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.train:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, net)
             except Exception as ex:  # the checker failing must not hide the GPU number

@@ -9,10 +9,10 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 step() { echo "[evidence] $1 ($(date +%T))"; }
 
-step "bench.py, default flags"
-( time python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time
-step "kernel trace of bench.py --no-extras --no-cpu-baseline"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_bench -o kt -- python3 $R/bench.py --no-extras --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/kt_bench.err
+step "bench.py --full"
+( time python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time
+step "kernel trace of bench.py --full --no-extras --no-cpu-baseline"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_bench -o kt -- python3 $R/bench.py --full --no-extras --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/kt_bench.err
 step "kernel trace of the training step: on one stream (the kernels' own durations), then as it runs (what overlaps)"
 TG_TRAIN_ONE_STREAM=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_train -o kt -- python3 $R/scripts/train_step_ab.py 10 > $O/train_step_one_stream_under_rocprof.json 2> $O/kt_train.err
 rocprofv3 --kernel-trace --output-format csv -d $O/kt_train2 -o kt -- python3 $R/scripts/train_step_ab.py 12 --driver > /dev/null 2> $O/kt_train2.err

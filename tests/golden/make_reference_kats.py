@@ -3,7 +3,8 @@
 
 Reads (as text) /root/reference/{tak/tests/{perft,wins,tps,symm}.rs, alpha-tak/src/repr/tests.rs,
 alpha-tak/src/search/move_map.rs}.  Only DATA is kept: PTN move lists, expected counts / results /
-strings / planes, seeds, and the sha256 of the legacy 5×5 move table (not the table itself).
+strings / planes, seeds, and the sha256 of the legacy 5×5 move table; the table's 1575 move strings
+themselves go to tests/golden/legacy5_moves.json.
 Run in the build container (the reference is not present on the GPU box); the JSON is committed.
 """
 import hashlib
@@ -110,6 +111,10 @@ kats["legacy5"] = {
     "sha256_newline_joined": hashlib.sha256("\n".join(table).encode()).hexdigest(),
     "spot": {str(i): table[i] for i in (0, 1, 2, 74, 75, 76, 77, 105, 500, 1000, 1574)},
 }
+# the whole table as data, so that the oracle's rule-generated table is compared move by move without the reference present
+with open(os.path.join(os.path.dirname(OUT), "legacy5_moves.json"), "w") as f:
+    json.dump({"source": "POSSIBLE_MOVES_IN_5S, alpha-tak/src/search/move_map.rs (data only)", "moves": table}, f, indent=0)
+    f.write("\n")
 
 with open(OUT, "w") as f:
     json.dump(kats, f, indent=1)

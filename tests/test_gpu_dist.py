@@ -145,7 +145,7 @@ def test_bench_gpus_2_runs_unaided_on_one_card():
     env.update(TAK_BENCH_BACKEND="gloo", OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--games", "256", "--rollouts", "24",
            "--blocks", "2", "--filters", "64", "--train-games", "256", "--train-blocks", "2", "--train-filters", "64", "--train-steps", "2",
-           "--train-chunk", "40", "--train-chunks-in-step", "2", "--train-example-rollouts", "8", "--profile-every", "0"]
+           "--train-chunk", "40", "--train-chunks-in-step", "2", "--train-example-rollouts", "8", "--profile-every", "0", "--full"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -182,7 +182,7 @@ def test_bench_gpus_4_runs_unaided_on_one_card():
     env.update(TAK_BENCH_BACKEND="gloo", OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "1", "--games", "128", "--rollouts", "16",
            "--blocks", "2", "--filters", "64", "--train-games", "128", "--train-blocks", "2", "--train-filters", "64", "--train-steps", "2",
-           "--train-chunk", "24", "--train-chunks-in-step", "2", "--train-example-rollouts", "8", "--profile-every", "0"]
+           "--train-chunk", "24", "--train-chunks-in-step", "2", "--train-example-rollouts", "8", "--profile-every", "0", "--full"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
