@@ -24,6 +24,7 @@ def test_policy_eval_and_training_edges(orc):
     p, v = e.policy_eval(sts)                                               # 300 positions through an engine of 48: chunks, the split tower
     pr, vr = torch_ref.forward(net, orc.encode(n, sts))
     assert np.abs(p - pr).max() <= 1e-4 and np.abs(v - vr).max() <= 1e-4
+    torch_ref.report("api edges: 300 positions through an engine of 48", torch_ref.check_forward(p, v, torch_ref.forward64(net, orc.encode(n, sts)), "f32", "api edges"))
     p49, v49 = e.policy_eval(sts[:49])
     assert np.array_equal(p49, p[:49]) and np.array_equal(v49, v[:49])
     e.train_create(chunk_size=16, chunks_in_step=2)

@@ -50,9 +50,18 @@ def test_policy_eval_full_batch_properties(c2, orc):
         worst_v = max(worst_v, float(np.abs(v[lo : lo + 512] - v_ref).max()))
     print(f"c2_f32 (randomised BatchNorm fold): worst |dp| {worst_p:.3e}, worst |dv| {worst_v:.3e} over all {G} rows")
     assert worst_p <= 1e-4 and worst_v <= 1e-4, (worst_p, worst_v)
+    _fp64_gate(orc, "c2_f32 full batch", net, 5, sts, p, v, "f32", 512)
 
 
-def _all_rows_against_pytorch(orc, n, blocks, filters, head, precision, rows, seed, chunk=512):
+def _fp64_gate(orc, name, net, n, sts, p, v, precision, rows):
+    """torch_ref.check_forward against the fp64 forward on a fixed seeded subset of `rows` rows of the batch (fp64 of every row of
+    the widest networks would cost the CPU more than the suite's budget)"""
+    sel = np.sort(np.random.default_rng(len(sts) + rows).choice(len(sts), rows, replace=False))
+    ref = torch_ref.forward64(net, orc.encode(n, sts[sel]))
+    return torch_ref.report(f"{name} ({rows} seeded rows of {len(sts)})", torch_ref.check_forward(p[sel], v[sel], ref, precision, name))
+
+
+def _all_rows_against_pytorch(orc, n, blocks, filters, head, precision, rows, seed, chunk=512, name=None):
     """policy_eval on a FULL batch of 4096 positions (the kernel instantiations the benchmarks run) against PyTorch fp32 on
     `rows` (all 4096, or every 4th): worst |Δ| of policy and eval (north_star: ≤ 1e-4).  BatchNorm's affine parameters and running
     statistics are randomised (round 5), so the fold is not the identity."""
@@ -68,6 +77,7 @@ def _all_rows_against_pytorch(orc, n, blocks, filters, head, precision, rows, se
     p, v = e.policy_eval(sts)
     e.close()
     assert np.abs(p.sum(1) - 1).max() < 2e-5 and (p > 0).all() and (np.abs(v) <= 1).all()
+    _fp64_gate(orc, name, net, n, sts, p, v, precision, 256 if n == 5 else 128)
     idx = np.arange(0, G, G // rows)
     worst_p = worst_v = 0.0
     for lo in range(0, len(idx), chunk):
@@ -94,7 +104,7 @@ def _all_rows_against_pytorch(orc, n, blocks, filters, head, precision, rows, se
     ("c3_bf16x3", 6, 10, 128, "conv", "bf16x3", 1024),
 ])
 def test_full_batch_rows_against_pytorch(orc, name, n, blocks, filters, head, precision, rows):
-    worst_p, worst_v = _all_rows_against_pytorch(orc, n, blocks, filters, head, precision, rows, seed=3, chunk=512 if n == 5 else 128)
+    worst_p, worst_v = _all_rows_against_pytorch(orc, n, blocks, filters, head, precision, rows, seed=3, chunk=512 if n == 5 else 128, name=name)
     print(f"{name}: worst |dp| {worst_p:.3e}, worst |dv| {worst_v:.3e} over {rows} rows of a 4096-position batch")
     assert worst_p <= 1e-4 and worst_v <= 1e-4, (name, worst_p, worst_v)
 
@@ -172,6 +182,7 @@ def test_sixteen_thousand_games_forward_search_and_selfplay(orc):
         worst_v = max(worst_v, float(np.abs(v[lo : lo + 1024] - v_ref).max()))
     print(f"c2_f32 at 16384 rows: worst |dp| {worst_p:.3e}, worst |dv| {worst_v:.3e} over all {G4} distinct rows")
     assert worst_p <= 1e-4 and worst_v <= 1e-4, (worst_p, worst_v)
+    _fp64_gate(orc, "c2_f32 at 16384 rows", net, 5, sts, p, v, "f32", 512)
     # the 4096-row batch of the same positions returns the same bits: a row does not know how wide its batch is
     p4, v4 = e.policy_eval(sts[5000 : 5000 + G])
     assert np.array_equal(p4, p[5000 : 5000 + G]) and np.array_equal(v4, v[5000 : 5000 + G])
@@ -309,6 +320,7 @@ def test_config_c3_full_size(orc):
         worst_v = max(worst_v, float(np.abs(v[sel] - v_ref).max()))
     print(f"c3_f32 (randomised BatchNorm fold): worst |dp| {worst_p:.3e}, worst |dv| {worst_v:.3e} over all {G} rows")
     assert worst_p <= 1e-4 and worst_v <= 1e-4, (worst_p, worst_v)
+    _fp64_gate(orc, "c3_f32 full batch", net, n, sts, p, v, "f32", 128)
     p2, v2 = e.policy_eval(np.roll(sts, 1000, axis=0)[:1024])              # the same positions in other slots of another batch size
     assert np.array_equal(p2[1000:], p[:24]) and np.array_equal(v2[1000:], v[:24])
     iters = 12

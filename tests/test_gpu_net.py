@@ -40,6 +40,10 @@ def test_golden_fixture(path, orc):
     p2, v2 = e.forward_mcts(orc.encode(n, z["states"]))
     assert np.abs(p - p2).max() <= 1e-6 and np.abs(v - v2).max() <= 1e-6
     assert np.abs(p2 - z["policy"]).max() <= TOL and np.abs(v2 - z["eval"]).max() <= TOL
+    ref = torch_ref.forward64(net, orc.encode(n, z["states"]))
+    name = os.path.basename(path)[:-4]
+    torch_ref.report(f"golden {name} policy_eval", torch_ref.check_forward(p, v, ref, "f32", name))
+    torch_ref.report(f"golden {name} forward_mcts", torch_ref.check_forward(p2, v2, ref, "f32", name + " planes"))
     e.close()
 
 
@@ -63,6 +67,8 @@ def test_config_topologies_vs_torch(orc, n, blocks, filters, head, batch):
     assert np.abs(v - v_ref).max() <= TOL, np.abs(v - v_ref).max()
     # relative check on the policy too (probabilities are ~1e-3, so 1e-4 absolute alone is lax)
     assert (np.abs(p - p_ref) / p_ref).max() < 5e-4
+    torch_ref.report(f"topology {n}x{n} {blocks}x{filters} {head} B={batch} f32",
+                     torch_ref.check_forward(p, v, torch_ref.forward64(net, orc.encode(n, sts)), "f32", "topology"))
     # per-position results do not depend on the batch they are evaluated in
     p1, v1 = e.policy_eval(sts[3:4])
     assert np.array_equal(p1[0], p[3]) and v1[0] == v[3]
@@ -96,11 +102,16 @@ def test_bf16x3_tower_within_tolerance(orc, n, blocks, filters, head, batch):
     p2, v2 = e.forward_mcts(orc.encode(n, sts))  # (planes entry: every plane through layer 0 — another summation order)
     assert np.abs(p - p2).max() <= 2e-5 and np.abs(v - v2).max() <= 2e-5
     assert np.abs(p2 - p_ref).max() <= TOL and np.abs(v2 - v_ref).max() <= TOL
+    ref = torch_ref.forward64(net, orc.encode(n, sts))
+    tag = f"{n}x{n} {blocks}x{filters} {head} B={batch}"
+    torch_ref.report(f"bf16x3 tower {tag} policy_eval", torch_ref.check_forward(p, v, ref, "bf16x3", "bf16x3 states"))
+    torch_ref.report(f"bf16x3 tower {tag} forward_mcts", torch_ref.check_forward(p2, v2, ref, "bf16x3", "bf16x3 planes"))
     # back to the exact path on the same engine
     e.set_precision("f32")
     e.load_state_dict(torch_ref.abi_tensors(net))
     pf, vf = e.policy_eval(sts)
     assert np.abs(pf - p_ref).max() <= TOL and not np.array_equal(pf, p)
+    torch_ref.report(f"bf16x3 tower test, f32 path {tag}", torch_ref.check_forward(pf, vf, ref, "f32", "f32 after bf16x3"))
     print(f"bf16x3 vs torch: policy rel {(np.abs(p - p_ref) / p_ref).max():.2e}, eval abs {np.abs(v - v_ref).max():.2e}; "
           f"f32: policy rel {(np.abs(pf - p_ref) / p_ref).max():.2e}, eval abs {np.abs(vf - v_ref).max():.2e}")
     e.close()
@@ -175,6 +186,7 @@ def test_default_init_matches_tch_defaults_and_torch_forward(orc, n, head):
     pol, ev = e.policy_eval(states)
     rp, rv = torch_ref.forward(net, orc.encode(n, states))
     assert np.abs(pol - rp).max() <= TOL and np.abs(ev - rv).max() <= TOL
+    torch_ref.report(f"default init {n}x{n} {head}", torch_ref.check_forward(pol, ev, torch_ref.forward64(net, orc.encode(n, states)), "f32", "default init"))
     e.close()
 
 
@@ -286,6 +298,10 @@ def test_planes_entry_equals_states_entry_at_full_batch(orc, n, blocks, filters,
     p_ref, v_ref = torch_ref.forward(net, orc.encode(n, sts[:256]))
     for pp, vv in ((p, v), (p2, v2)):
         assert np.abs(pp[:256] - p_ref).max() <= TOL and np.abs(vv[:256] - v_ref).max() <= TOL
+    ref = torch_ref.forward64(net, orc.encode(n, sts[:256]))
+    for entry, pp, vv in (("policy_eval", p, v), ("forward_mcts", p2, v2)):
+        torch_ref.report(f"full batch {n}x{n} {head} B={batch} {precision} {entry}",
+                         torch_ref.check_forward(pp[:256], vv[:256], ref, precision, f"full batch {entry}"))
     e.close()
 
 
@@ -316,10 +332,12 @@ def test_checkpoint_archive_loads_into_the_engine(orc, tmp_path, n, blocks, filt
     assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
     p_ref, v_ref = torch_ref.forward(net, orc.encode(n, sts))
     assert np.abs(outs[1][0] - p_ref).max() <= 1e-4 and np.abs(outs[1][1] - v_ref).max() <= 1e-4
+    torch_ref.report(f"checkpoint archive {n}x{n} {head}",
+                     torch_ref.check_forward(*outs[1], torch_ref.forward64(net, orc.encode(n, sts)), "f32", "checkpoint archive"))
 
 
 @pytest.mark.parametrize("stem,n,blocks,filters", [("tch_net4_conv_1x32", 4, 1, 32), ("tch_net6_conv_1x32", 6, 1, 32)])
-def test_archive_written_by_libtorch_loads_into_the_engine(stem, n, blocks, filters):
+def test_archive_written_by_libtorch_loads_into_the_engine(orc, stem, n, blocks, filters):
     """N4 against the real container: tests/golden/tch_*.model were written by libtorch's OutputArchive (write + save_to: the
     calls behind tch's VarStore::save, tests/golden/tch_archive_writer.cpp), with tch-style variable names.  Archive →
     tak_amd.checkpoint → tg_net_set_tensor → tg_policy_eval must give the outputs recorded with PyTorch-CPU on the same
@@ -336,4 +354,8 @@ def test_archive_written_by_libtorch_loads_into_the_engine(stem, n, blocks, filt
     e.load_state_dict(loaded)
     p, v = e.policy_eval(exp["states"])
     assert np.abs(p - exp["policy"]).max() <= 1e-4 and np.abs(v - exp["value"]).max() <= 1e-4
+    # and against the fp64 forward of the tensors the archive held
+    net = torch_ref.load_abi_tensors(torch_ref.make_net(n, blocks, filters, "conv"), loaded)
+    torch_ref.report(f"libtorch archive {stem}",
+                     torch_ref.check_forward(p, v, torch_ref.forward64(net, orc.encode(n, exp["states"])), "f32", "libtorch archive"))
     e.close()

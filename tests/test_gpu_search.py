@@ -203,10 +203,23 @@ def test_one_pool_for_all_trees(orc):
 def test_tree_parity_with_real_network(orc, n, blocks, filters, head):
     # the oracle's MCTS evaluates its leaves through tg_policy_eval; the GPU search feeds the same
     # kernels from its own leaf batch — identical trees require identical per-position network outputs
+    _tree_parity_with_real_network(orc, n, blocks, filters, head, torch_ref.make_net(n, blocks, filters, head, seed=3))
+
+
+@pytest.mark.parametrize("n,blocks,filters,head", [(5, 2, 64, "fc5"), (6, 1, 128, "conv")])
+def test_tree_parity_with_a_trained_like_network(orc, n, blocks, filters, head):
+    """the same parity on torch_ref.make_trained_net: peaked priors (median largest p ≥ 0.2) and values near ±1 travel through whole trees
+    bit for bit — the backup's stat_exp at arguments down to −30 and beyond, selections decided by priors rather than by ties"""
+    import posgen
+
+    planes = orc.encode(n, posgen.distinct_positions(orc, n, 256, seed=41, max_plies=60))
+    _tree_parity_with_real_network(orc, n, blocks, filters, head, torch_ref.make_trained_net(n, blocks, filters, head, planes, seed=41))
+
+
+def _tree_parity_with_real_network(orc, n, blocks, filters, head, net):
     import tak_amd
 
     games = 12
-    net = torch_ref.make_net(n, blocks, filters, head, seed=3)
     tensors = torch_ref.abi_tensors(net)
     h = tak_amd.HEAD_FC5 if head == "fc5" else tak_amd.HEAD_CONV
     e = _mk(n, tak_amd.EVAL_RESNET, games, head=h, res_blocks=blocks, filters=filters)
@@ -388,6 +401,7 @@ def test_the_references_own_constants_net6_32_games(orc):
     p, v = e.policy_eval(sts)
     p_ref, v_ref = torch_ref.forward(net, orc.encode(n, sts))
     assert np.abs(p - p_ref).max() <= 1e-4 and np.abs(v - v_ref).max() <= 1e-4
+    torch_ref.report("reference constants Net6, 32 games", torch_ref.check_forward(p, v, torch_ref.forward64(net, orc.encode(n, sts)), "f32", "Net6 32 games"))
     p2, v2 = padded_eval(sts)
     assert np.array_equal(p, p2) and np.array_equal(v, v2)
     e.search_create(games, arena_nodes=1 << 15, seed=2)

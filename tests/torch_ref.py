@@ -206,3 +206,190 @@ def engine_relu_decisions(engine, layers, positions, n, filters):
     rows = positions * n * n
     return [torch.from_numpy(engine.train_debug_read("y", l, (rows, filters)) > 0).reshape(positions, n, n, filters).permute(0, 3, 1, 2)
             for l in range(layers)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# fp64 reference and the forward gates.  make_net's default-initialised networks have an almost flat policy (largest p ≈ 1e-3, on 6×6
+# ≈ 3e-4) and |v| < 0.4, so an absolute 1e-4 gate on p cannot see a dropped bias or a per-mille mis-scale.  The gates below work in log
+# space against a float64 forward, and make_trained_net builds networks whose outputs look like a trained one's: peaked policies,
+# saturated values, BatchNorm channels whose running variance is of the order of eps.
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+LOGP_FLOOR = -30.0   # below it an entry is "tiny": only 0 ≤ p ≤ TINY_P is asked of it
+TINY_P = 1e-12
+
+# One set of constants per precision.  For every entry with log p64 ≥ LOGP_FLOOR:  |log p − log p64| ≤ a + b·|log p64|;  per row
+# Σ|p − p64| / 2 ≤ t;  |v − v64| ≤ c·(1 − v64²) + 2⁻²³  (c bounds the error of the value's pre-activation, tanh′ = 1 − v²).
+# b comes from the arithmetic, not from a fit: the FC path's softmax takes exp(x − M) as v_exp_f32((x − M)·log2 e) (softmax.cuh, stat_exp);
+# the rounding of x − M and of the product by log2 e are each ≤ 2⁻²⁴ relative, i.e. ≤ 2⁻²⁴·|x − M| ≤ 2⁻²⁴·|log p| in the natural log:
+# b = 2·log2 e·2⁻²⁴ (≈ 1.7e-7) covers both with the log2 e factor of the base-2 form to spare.
+# a, t and c sit about 3× above the engine's worst error measured on an MI355X over the whole GPU suite (every case check_forward,
+# check_logp or check_priors gates — the trained-like sweep of tests/test_gpu_fp64.py sets every maximum):
+#              worst |Δlog p| − b·|log p64|          worst row TV                  worst |Δv| − 2⁻²³ over (1 − v64²)
+#   f32        6.5e-5 (5×5×128 FC, planes, B=65)     7.3e-6 (5×5×128 FC, B=1300)   9.8e-6 (5×5×128 FC, B=513)
+#   bf16x3     3.1e-4 (6×6×128 conv, planes, B=700)  3.9e-5 (6×6×128 conv, B=700)  9.8e-5 (5×5×64 FC, B=2400)
+# (PyTorch's own fp32 forward on the same kind of networks: ≤ 1.3e-5, 2.1e-6, 5.9e-6.)  The teeth test (tests/test_forward_gates.py)
+# rejects each of its mutations under both sets; the smallest of them, a value bias off by 1e-3, is 1e-3 of pre-activation error.
+_B_EXP = 2.0 * 1.4426950408889634 * 2.0 ** -24
+GATES = {
+    "f32": dict(a=2e-4, b=_B_EXP, t=2e-5, c=3e-5),
+    "bf16x3": dict(a=1e-3, b=_B_EXP, t=1e-4, c=3e-4),
+}
+
+
+def _layers64(net, x, training):
+    """shared body of the fp64 forwards: (tower output s, policy logits, value pre-activation), all float64 tensors"""
+    import copy
+
+    n64 = copy.deepcopy(net).double()
+    n64.train(training)
+    s = F.relu(n64.bn0(n64.conv0(x)))
+    for blk in n64.res:
+        s = blk(s)
+    flat = s.reshape(s.shape[0], -1)
+    logits = n64.policy(flat) if n64.head == "fc5" else n64.policy(s).reshape(s.shape[0], -1)
+    return logits, n64.value(flat)[:, 0]
+
+
+@torch.no_grad()
+def forward64(net, planes, training=False, chunk=512):
+    """float64 forward of `net` on `planes`: BatchNorm in eval mode (forward_mcts) or, training=True, on the batch's own statistics
+    (forward_training; one batch, not chunked).  → dict(logits, logp = log_softmax over all outputs, pre = the value's pre-activation,
+    v = tanh(pre)), float64 numpy arrays."""
+    planes = np.ascontiguousarray(planes, np.float64)
+    step = len(planes) if training else chunk
+    parts = [_layers64(net, torch.from_numpy(planes[lo: lo + step]), training) for lo in range(0, max(len(planes), 1), step)]
+    logits = torch.cat([p[0] for p in parts])
+    pre = torch.cat([p[1] for p in parts])
+    return dict(logits=logits.numpy(), logp=torch.log_softmax(logits, dim=1).numpy(), pre=pre.numpy(), v=torch.tanh(pre).numpy())
+
+
+def slice_ref(ref, sel):
+    return {k: v[sel] for k, v in ref.items()}
+
+
+def _policy_metrics(p, logp64, g, mask=None):
+    """log-space and tiny-entry metrics of probabilities p against log p64 (same shape; mask = entries that take part)"""
+    p = np.asarray(p, np.float64)
+    keep = np.ones(p.shape, bool) if mask is None else mask
+    big = keep & (logp64 >= LOGP_FLOOR)
+    tiny = keep & (logp64 < LOGP_FLOOR)
+    with np.errstate(divide="ignore"):
+        d = np.abs(np.log(np.where(big, p, 1.0)) - np.where(big, logp64, 0.0))
+    excess = np.where(big, d - g["b"] * np.abs(logp64), -np.inf)
+    bad = np.argwhere(excess > g["a"])
+    tv = 0.5 * np.where(keep, np.abs(p - np.exp(logp64)), 0.0).sum(axis=-1)
+    m = dict(logp_abs=float(d[big].max()) if big.any() else 0.0, logp_a=float(max(excess.max(), 0.0)) if big.any() else 0.0,
+             tv=float(tv.max()) if tv.size else 0.0, tiny_max=float(p[tiny].max()) if tiny.any() else 0.0,
+             tiny_neg=bool((p[tiny] < 0).any()) if tiny.any() else False, entries=int(big.sum()), tiny_entries=int(tiny.sum()),
+             first_bad=tuple(int(i) for i in bad[0]) if len(bad) else None)
+    return m
+
+
+def _assert_policy(m, g, what):
+    assert m["first_bad"] is None, (f"{what}: |log p − log p64| beyond a + b·|log p64| at {m['first_bad']} "
+                                    f"(worst excess {m['logp_a']:.3e} > a = {g['a']:.1e})")
+    assert not m["tiny_neg"] and m["tiny_max"] <= TINY_P, f"{what}: an entry with log p64 < {LOGP_FLOOR} has p = {m['tiny_max']:.3e}"
+    assert m["tv"] <= g["t"], f"{what}: row total variation {m['tv']:.3e} > t = {g['t']:.1e}"
+
+
+def check_forward(p, v, ref, precision, what="forward"):
+    """The forward gates of `precision` (GATES) on an engine's (or any) probabilities p [B, P] and values v [B] against forward64's `ref`
+    (the same rows).  Asserts, naming `what` and the gate that failed; returns the measured metrics."""
+    g = GATES[precision]
+    p = np.asarray(p)
+    assert p.shape == ref["logp"].shape and np.shape(v) == ref["v"].shape, (what, p.shape, ref["logp"].shape)
+    m = _policy_metrics(p, ref["logp"], g)
+    dv = np.abs(np.asarray(v, np.float64) - ref["v"])
+    slope = 1.0 - ref["v"] ** 2
+    pre = np.maximum(dv - 2.0 ** -23, 0.0) / np.maximum(slope, 1e-300)
+    m.update(v_abs=float(dv.max()) if dv.size else 0.0, pre=float(pre.max()) if pre.size else 0.0,
+             v_max=float(np.abs(ref["v"]).max()) if dv.size else 0.0, rows=int(p.shape[0]))
+    _assert_policy(m, g, what)
+    assert (dv <= g["c"] * slope + 2.0 ** -23).all(), (f"{what}: |v − v64| beyond c·(1 − v64²) + 2⁻²³ "
+                                                       f"(implied pre-tanh error {m['pre']:.3e} > c = {g['c']:.1e})")
+    return m
+
+
+def check_logp(logp, ref, precision, what="log_softmax"):
+    """check_forward's policy gates on log-probabilities (forward_training's output) instead of probabilities"""
+    g = GATES[precision]
+    m = _policy_metrics(np.exp(np.asarray(logp, np.float64)), ref["logp"], g)
+    _assert_policy(m, g, what)
+    return m
+
+
+def check_priors(prior, logp64, mask, precision, what="priors"):
+    """the policy gates on the entries of p64 a tree's children carry (prior[g, i] against logp64[g, i] where mask[g, i])"""
+    g = GATES[precision]
+    m = _policy_metrics(np.where(mask, prior, 0.0), np.where(mask, logp64, 0.0), g, mask=mask)
+    _assert_policy(m, g, what)
+    return m
+
+
+def report(name, m):
+    """one line per gated case (the table of DESIGN.md §4 is read off these)"""
+    keys = ("logp_a", "logp_abs", "tv", "tiny_max", "pre", "v_abs", "v_max", "rows")
+    print("fp64-gate " + name + ": " + ", ".join(f"{k} {m[k]:.3e}" if isinstance(m[k], float) else f"{k} {m[k]}" for k in keys if k in m),
+          flush=True)
+    return m
+
+
+@torch.no_grad()
+def make_trained_net(n, res_blocks, filters, head, planes, seed=0, logit_std=3.0, value_std=1.5, quiet_layers=None, quiet_channels=2):
+    """A network whose outputs look like a trained one's, built around make_net's random weights (make_net itself stays as it is):
+      * BatchNorm running statistics are the network's own activations on `planes` (one training-mode pass, momentum 1);
+      * in `quiet_layers` (default: conv0, the first block's conv1, the last conv) `quiet_channels` output channels are nearly constant:
+        their conv weights are scaled so the running variance lands near 3e-5 (≤ 1e-4, the order of eps = 1e-5), while the normalised
+        output stays O(1) — so eps, and the host fold's rounding of var + eps, change the result visibly;
+      * the policy logits have a standard deviation of `logit_std` over the batch, widened in steps of 10 % until the median largest
+        probability is ≥ 0.2 (a peaked policy), with a bias of its own of the order of 1;
+      * the value pre-activation has a standard deviation of `value_std` (some |v| ≥ 0.99).
+    Returns the network in eval mode."""
+    net = make_net(n, res_blocks, filters, head, seed=seed, randomize_bn=True)
+    g = torch.Generator().manual_seed(seed + 7)
+    x = torch.from_numpy(np.ascontiguousarray(planes, np.float32))
+    convs = [net.conv0] + [c for blk in net.res for c in (blk.conv1, blk.conv2)]
+    bns = [net.bn0] + [b for blk in net.res for b in (blk.bn1, blk.bn2)]
+    if quiet_layers is None:
+        quiet_layers = sorted({0, 1 if res_blocks else 0, len(convs) - 1})
+
+    def calibrate():
+        for m in bns:
+            m.momentum = 1.0
+        net.train()
+        net.forward_training(x)
+        net.eval()
+
+    for li in quiet_layers:
+        calibrate()
+        var = bns[li].running_var
+        ch = torch.randperm(filters, generator=g)[:quiet_channels]
+        for c in ch.tolist():
+            s = float(np.sqrt(3e-5 / max(float(var[c]), 1e-12)))
+            convs[li].weight[c] *= s
+            convs[li].bias[c] *= s
+    calibrate()
+    for m in bns:
+        m.momentum = 0.1
+    # heads: scale to the wanted spreads, then give the policy a bias of the order of its logits
+    s = F.relu(net.bn0(net.conv0(x)))
+    for blk in net.res:
+        s = blk(s)
+    flat = s.reshape(s.shape[0], -1)
+    logits = net.policy(flat) if head == "fc5" else net.policy(s).reshape(s.shape[0], -1)
+    bias = torch.randn(net.policy.bias.shape, generator=g) * 0.5 * logit_std / 3.0
+    raw = logits - net.policy.bias if head == "fc5" else logits - net.policy.bias.repeat_interleave(n * n)
+    full_bias = bias if head == "fc5" else bias.repeat_interleave(n * n)
+    k = logit_std / float(raw.std())
+    for _ in range(20):  # a little wider where the spread alone leaves the policy flatter than a trained one's
+        if float(torch.softmax(k * raw + full_bias, dim=1).max(dim=1).values.median()) >= 0.2:
+            break
+        k *= 1.1
+    net.policy.weight *= k
+    net.policy.bias.copy_(bias)
+    pre = net.value(flat)[:, 0]
+    kv = value_std / float(pre.std())
+    net.value.weight *= kv
+    net.value.bias.copy_(0.2 - kv * (pre.mean() - net.value.bias))  # centred: the pre-activation spans about ±4
+    return net.eval()
