@@ -43,11 +43,11 @@ step "forward micro-benchmarks"
 for c in c2 c3 c5; do python3 $R/scripts/ab_forward.py $c 2>/dev/null | grep cfg; done > $O/ab_forward.jsonl
 step "summaries"
 P=python3
-$P $R/scripts/pmc_traffic.py $(find $O/pmc_traffic -name '*counter_collection.csv' | head -1) k_tower_halo 27262976 $O/pmc_traffic_k_tower_halo.json > /dev/null
+$P $R/scripts/pmc_traffic.py $(find $O/pmc_traffic -name '*counter_collection.csv' | head -1) k_tower_sq 27262976 $O/pmc_traffic_k_tower_sq.json > /dev/null
 $P $R/scripts/pmc_traffic.py $(find $O/pmc_traffic -name '*counter_collection.csv' | head -1) k_fc_ring 36836352 $O/pmc_traffic_k_fc_ring.json > /dev/null
 # search loop: activations 26.2 MB + the 99 tiles' weights 10.1 MB + child_pidx 1.0 MB in, children's logits 0.7 MB + statistics 0.4 MB out
 $P $R/scripts/pmc_traffic.py $(find $O/pmc_traffic_bench -name '*counter_collection.csv' | head -1) k_fc_ring 38563840 $O/pmc_traffic_k_fc_ring_gather.json > /dev/null
-for d in pmc_sq1 pmc_sq2; do $P $R/scripts/pmc_summary.py $(find $O/$d -name '*counter_collection.csv' | head -1) k_tower_halo k_fc_ring; done > $O/pmc_sq_tower_fc.txt
+for d in pmc_sq1 pmc_sq2; do $P $R/scripts/pmc_summary.py $(find $O/$d -name '*counter_collection.csv' | head -1) k_tower_sq k_fc_ring; done > $O/pmc_sq_tower_fc.txt
 $P $R/scripts/pmc_summary.py $(find $O/pmc_tree -name '*counter_collection.csv' | head -1) k_backup_select k_select k_reroot > $O/pmc_tree_kernels.txt
 $P $R/scripts/pmc_summary.py $(find $O/pmc_board -name '*counter_collection.csv' | head -1) k_board_pass > $O/pmc_board_pass_instruction_mix.txt
 $P $R/scripts/pmc_summary.py $(find $O/pmc_board6 -name '*counter_collection.csv' | head -1) k_board_pass >> $O/pmc_board_pass_instruction_mix.txt

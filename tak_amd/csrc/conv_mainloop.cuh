@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <utility>
+
 namespace tg {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -272,6 +274,134 @@ __device__ __forceinline__ void conv_mainloop_halo(const f32x4* __restrict__ lds
 #endif
 #undef TG_HALO_OFF
 #undef TG_HALO_W
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same loop with ONE BOARD SQUARE PER ROW TILE (k_tower_sq, 5×5 boards, 16 positions per workgroup): tile = square
+// sq, column r16 = position r16 of the workgroup.  Every column of a tile then has the same taps on the board, and a
+// tap that leaves the board is skipped for the whole tile: 169 of the 225 (square, tap) products of a 5×5 board are
+// issued instead of all of them.  A skipped tap would only have added exact zeros (an off-board cell × a finite
+// weight) to each output's single chain over (tap, chunk), which keeps its order → the bits of conv_mainloop_halo.
+// Image: position-major, cell pitch F + 8 floats (sq_image_cell4), position pitch ≡ 2 (mod 16) slots of 16 B
+// (sq_image_pitch4): a main-loop read of one (square, tap, chunk) puts lane (position n, slot q) on bank group 2n + q + c,
+// so the ds_read_b128 lane groups {0-3,12-15,20-27}, … hit 16 distinct groups; layer 0's write of 16 consecutive rows
+// (squares) puts them on 2·sq + q + c: conflict free too (a pitch of F + 4 floats: 2.3-way).  No zero cells are needed (off-board taps are never read).  A lane keeps ONE
+// address (its position and slot q) and every (square, tap, chunk) is an immediate.
+// The square sets of the two row groups are compile-time (sq_tile): RG 0 = rows 0 – 1, squares 10, 11, 14 (86 on-board
+// taps), RG 1 = the rest (83); both hold interior squares, so both run all 36 (tap, chunk) steps and the weight stream
+// of conv_mainloop_halo is unchanged.  Each step's on-board tiles are split in two halves for the half-tile pipeline
+// (at least 6 per step: halves of ≥ 3 keep two MFMAs of a chain ≥ 64 cycles apart).
+// ------------------------------------------------------------------------------------------------
+constexpr int SQ_NB = 5;                                                          // board side of the square-tile tower
+template <int CH> constexpr int sq_image_cell4() { return 4 * CH + 2; }  // cell pitch in 16 B
+template <int CH> constexpr int sq_image_pitch4() {                         // position pitch in 16 B
+    constexpr int c = SQ_NB * SQ_NB * sq_image_cell4<CH>();
+    return c + ((2 - c) % 16 + 16) % 16;
+}
+static_assert(sq_image_pitch4<4>() == 450, "C2: 16 positions = 115 200 B");
+__host__ __device__ constexpr int sq_tiles(int rg) { return rg == 0 ? 13 : 12; }
+__host__ __device__ constexpr int sq_tile(int rg, int j) { return rg == 0 ? (j < 12 ? j : 14) : (j < 2 ? 12 + j : 13 + j); }
+__host__ __device__ constexpr bool sq_tap_on(int sq, int tap) {
+    const int y = sq / SQ_NB + tap / 3 - 1, x = sq % SQ_NB + tap % 3 - 1;
+    return y >= 0 && y < SQ_NB && x >= 0 && x < SQ_NB;
+}
+__host__ __device__ constexpr int sq_tap_count(int rg, int tap) {
+    int c = 0;
+    for (int j = 0; j < sq_tiles(rg); j++) c += sq_tap_on(sq_tile(rg, j), tap) ? 1 : 0;
+    return c;
+}
+// k-th tile (index into the row group's list) with tap `tap` on the board; -1 past the last
+__host__ __device__ constexpr int sq_tap_tile(int rg, int tap, int k) {
+    for (int j = 0; j < sq_tiles(rg); j++)
+        if (sq_tap_on(sq_tile(rg, j), tap) && k-- == 0) return j;
+    return -1;
+}
+static_assert(sq_tap_count(0, 0) + sq_tap_count(0, 1) + sq_tap_count(0, 2) + sq_tap_count(0, 3) + sq_tap_count(0, 4) + sq_tap_count(0, 5) +
+                      sq_tap_count(0, 6) + sq_tap_count(0, 7) + sq_tap_count(0, 8) == 86, "row group 0: 86 on-board taps");
+static_assert(sq_tap_count(1, 0) + sq_tap_count(1, 1) + sq_tap_count(1, 2) + sq_tap_count(1, 3) + sq_tap_count(1, 4) + sq_tap_count(1, 5) +
+                      sq_tap_count(1, 6) + sq_tap_count(1, 7) + sq_tap_count(1, 8) == 83, "row group 1: 83 on-board taps");
+
+// compile-time loop: f(std::integral_constant<int, i>) for i = 0 … N − 1 (the tile of every MFMA must be a constant, not a
+// value the optimiser may or may not fold: an acc[] indexed at run time lives in scratch)
+template <typename Fn, int... I>
+__device__ __forceinline__ void static_for_impl(Fn& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, typename Fn>
+__device__ __forceinline__ void static_for(Fn&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
+
+// img4 = this lane's base: lds4 + position·sq_image_pitch4 + q.  acc[j] = tile sq_tile(RG, j).
+template <int RG, int CH>
+__device__ __forceinline__ void conv_mainloop_sq(const f32x4* __restrict__ img4, const float* __restrict__ wlayer,
+                                                 const float* __restrict__ wnext, uint32_t wlane, f32x4 (&acc)[13], const int turn,
+                                                 f32x4& w0, f32x4& w1) {
+    constexpr int STEPS = 9 * CH, ROW = 3 * CH, CP4 = sq_image_cell4<CH>();
+    constexpr size_t WCHUNK = (size_t)16 * CH * 4 * 16;
+    static_assert(sq_tiles(RG) <= 13, "acc holds 13 tiles");
+#ifndef TG_PRIO_PERIOD
+#define TG_PRIO_PERIOD 2
+#endif
+    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wlayer, 0, (int)(9 * CH * WCHUNK), 0x00020000);
+    const __amdgpu_buffer_rsrc_t nrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wnext, 0, (int)(9 * CH * WCHUNK), 0x00020000);
+    // step s = tap·CH + chunk: its on-board tiles, the first ⌈cnt/2⌉ of them in half 1; the 16-byte image offset of the k-th
+    constexpr auto cnt = [](int s) { return sq_tap_count(RG, s / CH); };
+    constexpr auto h1 = [](int s) { return (sq_tap_count(RG, s / CH) + 1) / 2; };
+    constexpr auto off = [](int s, int k) {
+        return (sq_tile(RG, sq_tap_tile(RG, s / CH, k)) + (s / CH / 3 - 1) * SQ_NB + (s / CH % 3 - 1)) * CP4 + (s % CH) * 4;
+    };
+    f32x4 a1[7], a2[7];  // the two halves' fragments of a step (≤ 13 tiles on the board)
+    static_for<7>([&](auto K) {
+        constexpr int k = decltype(K)::value;
+        if constexpr (k < h1(0)) a1[k] = img4[off(0, k)];
+    });
+    static_for<STEPS>([&](auto S) {
+        constexpr int s = decltype(S)::value;
+#ifndef TG_NO_PRIO_TURNS
+        if constexpr (s % TG_PRIO_PERIOD == 0) {
+            if ((((s % ROW) / TG_PRIO_PERIOD + s / ROW) & 1) == turn) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+        }
+#endif
+        static_for<7>([&](auto K) {
+            constexpr int k = decltype(K)::value;
+            if constexpr (h1(s) + k < cnt(s)) a2[k] = img4[off(s, h1(s) + k)];
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<4>([&](auto T) {
+            static_for<7>([&](auto K) {
+                constexpr int t = decltype(T)::value, k = decltype(K)::value;
+                if constexpr (k < h1(s)) {
+                    constexpr int j = sq_tap_tile(RG, s / CH, k);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[t], a1[k][t], acc[j], 0, 0, 0);
+                }
+            });
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        // weights two chunks ahead; the last two steps request the next layer's chunks 0 and 1
+        f32x4 w2;
+        if constexpr (s < STEPS - 2) w2 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, (int)((s + 2) * WCHUNK), 0));
+        else w2 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(nrsrc, wlane, (int)((s - (STEPS - 2)) * WCHUNK), 0));
+        if constexpr (s + 1 < STEPS) {
+            static_for<7>([&](auto K) {
+                constexpr int k = decltype(K)::value;
+                if constexpr (k < h1(s + 1)) a1[k] = img4[off(s + 1, k)];
+            });
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<4>([&](auto T) {
+            static_for<7>([&](auto K) {
+                constexpr int t = decltype(T)::value, k = decltype(K)::value;
+                if constexpr (h1(s) + k < cnt(s)) {
+                    constexpr int j = sq_tap_tile(RG, s / CH, h1(s) + k);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[t], a2[k][t], acc[j], 0, 0, 0);
+                }
+            });
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        w0 = w1;
+        w1 = w2;
+    });
+#ifndef TG_NO_PRIO_TURNS
+    __builtin_amdgcn_s_setprio(0);
+#endif
 }
 
 // chunks 0 and 1 of a layer's weights for the first conv_mainloop_halo call of a kernel

@@ -98,6 +98,8 @@ constexpr int TOWER_SPLIT_MAX_BATCH = 128;  // 8 small workgroups per position: 
 bool tower_halo_geometry(int n, int F, int* pw, int* ps);
 void tower_halo_slotmap(int n, int pw, int ps, uint32_t* out /* ceil(pw·n²/16)·16 entries */);
 bool tower_supported(int n, int F, int cin_pad);
+// does a full batch of B positions run on the square-tile tower (k_tower_sq: MFMAs of on-board taps only, 169 of 225 on 5×5)?
+bool tower_square_tiles(int n, int F, int B);
 hipError_t launch_tower(hipStream_t st, const float* in, const TowerParams& T, float* out, int B, int n);
 hipError_t launch_tower_states(hipStream_t st, const uint8_t* states, const TowerParams& T, float* out, int B, int n, float* scratch = nullptr);
 // net_s3_kernels.hip — split-bf16 ("bf16x3") tower

@@ -629,9 +629,13 @@ static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const ui
         n->conv_rows = M;
         // algorithmic FLOPs of one timed launch: one F→F conv (per-layer path) or the whole tower (fused)
         n->conv_flops = (n->fused || n->s3) ? 2ll * M * 9 * ((long long)n->cin * F + 2ll * n->R * F * F) : 2ll * M * 9 * F * F;
-        // executed: with the constant planes as a bias layer 0 multiplies 16 + 4·cb_last_t input channels per tap, not cin
-        n->conv_flops_exec = (n->fused && !n->s3 && d_states && n->tower.cb)
-                                 ? 2ll * M * 9 * ((long long)(16 + 4 * n->tower.cb_last_t) * F + 2ll * n->R * F * F) : n->conv_flops;
+        // executed: with the constant planes as a bias layer 0 multiplies 16 + 4·cb_last_t input channels per tap, not cin; the
+        // square-tile tower issues the F → F layers' MFMAs of on-board (square, tap) pairs only (169 of 225 on 5×5)
+        if (n->fused && !n->s3) {
+            const long long c0 = (d_states && n->tower.cb) ? 16 + 4 * n->tower.cb_last_t : n->cin;
+            const long long taps = tower_square_tiles(N, F, nb) ? (long long)nb * 169 : 9ll * M;  // (row, tap) pairs of a layer ≥ 1
+            n->conv_flops_exec = 2ll * M * 9 * c0 * F + 2ll * taps * 2ll * n->R * F * F;
+        } else n->conv_flops_exec = n->conv_flops;
         chain->push_back(prof_event(n, st));
     }
     if (n->s3) {

@@ -16,6 +16,8 @@
 //                           off-board taps, per-tap masks): batches below 2048 / 1024 / 512 positions
 //   k_tower_halo            the same tower on the HALO image (zero cells between board rows and positions, taps as
 //                           ds_read immediates, conflict-free slot table): full batches, 89 – 94 % of the MFMA peak
+//   k_tower_sq              5×5 with 64 filters at full batches: layers ≥ 1 on square tiles (tile = board square, column =
+//                           position), only the MFMAs of on-board taps issued (169 of 225); same bits
 //   k_gemm                  generic GEMM
 //   k_fc_ring               policy FC for full batches: LDS-DMA ring of three K-steps, flag counters instead of barriers
 //   k_fc_small              policy FC for ≤ 2048 rows (no LDS, no barrier)
@@ -723,18 +725,15 @@ __global__ __launch_bounds__(NRT * CTW * 64) void k_tower_split(const uint8_t* _
 // invisible in the results, that keeps every ds_read_b128 of the loop off its neighbours' banks.
 // Per-element arithmetic (taps, chunks, k-steps, bias, ReLU, skip) in k_tower's order → identical bits.
 // ------------------------------------------------------------------------------------------------
-template <int RTW, int NWAVES, int CH0, int CH, int NB, bool FROM_STATES, bool CB = false>
-__global__ __launch_bounds__(NWAVES * 64) void k_tower_halo(const float* __restrict__ in, TowerParams T, float* __restrict__ out,
-                                                            int B, int PW, int CTW) {
-    static_assert(!CB || FROM_STATES, "the constant-plane bias needs the packed states");
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    f32x4* lds4 = (f32x4*)lds;
-    TG_STAMP(0, 6);  // kernel start (diagnostic build only)
-    constexpr int n = NB, nsq = NB * NB, RS = NB + 1, LEAD = NB + 2, F = 16 * CH, P4 = 4 * CH + 1;
-    const int PS = T.halo_ps;
+// Staging of the input planes and layer 0 on the plain image (tile t = rows 16t … 16t + 15), shared by the full-batch towers
+// k_tower_halo and k_tower_sq: leaves this wave's layer-0 outputs (bias and ReLU applied) of rows rho0 + 16j, j < my_tiles, in acc
+// and requests layer 1's first two chunks of weights into w0 / w1.  The caller synchronises before it overwrites the image.
+template <int RTW, int NWAVES, int CH0, int CH, int NB, bool FROM_STATES, bool CB>
+__device__ __forceinline__ void tower_plain_layer0(const float* __restrict__ in, const TowerParams& T, f32x4* lds4, int PW, int pos0,
+                                                   int npos, int CTW, uint32_t wlane, f32x4 (&acc)[RTW], int& rho0_out,
+                                                   int& my_tiles_out, f32x4& w0, f32x4& w1) {
+    constexpr int n = NB, nsq = NB * NB, F = 16 * CH;
     const int tid = threadIdx.x;
-    const int pos0 = blockIdx.x * PW;
-    const int npos = min(PW, B - pos0);
     const int rows = npos * nsq;
     const int wave = tid >> 6, lane = tid & 63;
     const int ct = wave % CTW, rg = wave / CTW;
@@ -798,36 +797,61 @@ __global__ __launch_bounds__(NWAVES * 64) void k_tower_halo(const float* __restr
     const int tile0 = rg * tbase + min(rg, trem);
     const bool short_group = my_tiles < RTW;
 
-    f32x4 acc[RTW];
 #pragma unroll
     for (int j = 0; j < RTW; j++) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
+    // ---- layer 0 ----
+    const int rho0 = tile0 * 16 + r16;
+    int vmask[RTW];
+    conv_tap_masks<RTW>(rows, n, nsq, rho0, vmask);
+    if (short_group) vmask[RTW - 1] = 0;
+    const f32x4* wp = (const f32x4*)(CB ? T.w0_board : T.w[0]) + ((size_t)(ch0 + r16) * 4 + q);
+    const int last_t0 = CB ? T.cb_last_t : T.cin_last_t;
+    TG_STAMP(0, 0);
+    if (RTW > 1 && short_group) {
+        f32x4 (&acs)[RTW - 1] = *reinterpret_cast<f32x4 (*)[RTW - 1]>(&acc[0]);
+        conv_mainloop<RTW - 1, CH0>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acs, last_t0);
+    } else {
+        conv_mainloop<RTW, CH0>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acc, last_t0);
+    }
+    TG_STAMP(0, 1);
+    if (T.nlayers > 1) conv_halo_first_weights<CH>(T.w[1], wlane, w0, w1);  // in flight during the change of images
+    const f32x4 bv = *(const f32x4*)&T.b[0][ch0 + 4 * q];
+#pragma unroll
+    for (int j = 0; j < RTW; j++) {
+        f32x4 v = acc[j] + (CB ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 >> 2) + q)] : bv);
+        v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
+        acc[j] = v;
+    }
+    rho0_out = rho0;
+    my_tiles_out = my_tiles;
+}
+
+template <int RTW, int NWAVES, int CH0, int CH, int NB, bool FROM_STATES, bool CB = false>
+__global__ __launch_bounds__(NWAVES * 64) void k_tower_halo(const float* __restrict__ in, TowerParams T, float* __restrict__ out,
+                                                            int B, int PW, int CTW) {
+    static_assert(!CB || FROM_STATES, "the constant-plane bias needs the packed states");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    f32x4* lds4 = (f32x4*)lds;
+    TG_STAMP(0, 6);  // kernel start (diagnostic build only)
+    constexpr int n = NB, nsq = NB * NB, RS = NB + 1, LEAD = NB + 2, F = 16 * CH, P4 = 4 * CH + 1;
+    const int PS = T.halo_ps;
+    const int tid = threadIdx.x;
+    const int pos0 = blockIdx.x * PW;
+    const int npos = min(PW, B - pos0);
+    const int rows = npos * nsq;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int ct = wave % CTW;
+    const int r16 = lane & 15, q = lane >> 4;
+    const int ch0 = ct * 16;
     const uint32_t wlane = (uint32_t)(((ch0 + r16) * 4 + q) * 16);  // this lane's 16 B inside a chunk of weights
     f32x4 w0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, w1 = w0;                // the weight stream's two chunks in flight between layers
-    // ---- layer 0 on the plain image: tile t = rows 16t … 16t + 15 ----
+    f32x4 acc[RTW];
+    int rho0, my_tiles;
+    tower_plain_layer0<RTW, NWAVES, CH0, CH, NB, FROM_STATES, CB>(in, T, lds4, PW, pos0, npos, CTW, wlane, acc, rho0, my_tiles, w0, w1);
+    const bool short_group = my_tiles < RTW;
+    const int tile0 = (rho0 - r16) >> 4;
     {
-        const int rho0 = tile0 * 16 + r16;
-        int vmask[RTW];
-        conv_tap_masks<RTW>(rows, n, nsq, rho0, vmask);
-        if (short_group) vmask[RTW - 1] = 0;
-        const f32x4* wp = (const f32x4*)(CB ? T.w0_board : T.w[0]) + ((size_t)(ch0 + r16) * 4 + q);
-        const int last_t0 = CB ? T.cb_last_t : T.cin_last_t;
-        TG_STAMP(0, 0);
-        if (RTW > 1 && short_group) {
-            f32x4 (&acs)[RTW - 1] = *reinterpret_cast<f32x4 (*)[RTW - 1]>(&acc[0]);
-            conv_mainloop<RTW - 1, CH0>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acs, last_t0);
-        } else {
-            conv_mainloop<RTW, CH0>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acc, last_t0);
-        }
-        TG_STAMP(0, 1);
-        if (T.nlayers > 1) conv_halo_first_weights<CH>(T.w[1], wlane, w0, w1);  // in flight during the change of images
-        const f32x4 bv = *(const f32x4*)&T.b[0][ch0 + 4 * q];
-#pragma unroll
-        for (int j = 0; j < RTW; j++) {
-            f32x4 v = acc[j] + (CB ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 >> 2) + q)] : bv);
-            v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
-            acc[j] = v;
-        }
         TG_STAMP(0, 2);
         __syncthreads();  // every wave has finished reading the input planes
         TG_STAMP(0, 3);
@@ -906,6 +930,131 @@ __global__ __launch_bounds__(NWAVES * 64) void k_tower_halo(const float* __restr
             lds4[cell4[j]] = acc[j];
             acc[j] = x0;
         }
+        TG_STAMP(layer, 4);
+        __syncthreads();
+        TG_STAMP(layer, 5);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The fused tower of 5×5 boards with 64 filters at full batches (16 positions per workgroup): staging and layer 0 as in
+// k_tower_halo, layers 1 … on the square-tile image of conv_mainloop_sq — row tile = board square, tile column = position
+// of the workgroup — whose main loop issues the MFMAs of the on-board taps only: 169 of the 225 (square, tap) pairs.
+// Waves w = 4·rg + ct: channel tile ct, row group rg (its squares: sq_tile); waves w and w + 4 share a SIMD.
+// Per-element arithmetic in k_tower's order, minus additions of exact zeros → identical bits.
+// ------------------------------------------------------------------------------------------------
+// the last layer's outputs of this lane's position p (one contiguous KB per tile in the FC's fragment order)
+template <int RG, int CH>
+__device__ __forceinline__ void tower_sq_store(const f32x4 (&acc)[13], const TowerParams& T, float* __restrict__ out, int p, int q, int ct) {
+    constexpr int nsq = SQ_NB * SQ_NB;
+#pragma unroll
+    for (int j = 0; j < sq_tiles(RG); j++) {
+        const int sq = sq_tile(RG, j);
+        if (T.frag_out) ((f32x4*)out)[((size_t)(p >> 4) * (nsq * CH) + sq * CH + ct) * 64 + (p & 15) * 4 + q] = acc[j];
+        else *(f32x4*)&out[((size_t)p * nsq + sq) * (16 * CH) + ct * 16 + 4 * q] = acc[j];
+    }
+}
+// a layer's outputs into the image; conv1 → acc = the block input the next layer (conv2) starts from
+template <int RG, int CH>
+__device__ __forceinline__ void tower_sq_writeback(f32x4* cell4, f32x4 (&acc)[13], bool conv1) {
+#pragma unroll
+    for (int j = 0; j < sq_tiles(RG); j++) {
+        const int o = sq_tile(RG, j) * sq_image_cell4<CH>();
+        f32x4 x0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (conv1) x0 = cell4[o];
+        cell4[o] = acc[j];
+        acc[j] = x0;
+    }
+}
+
+template <int CH0, bool FROM_STATES, bool CB = false>
+__global__ __launch_bounds__(512) void k_tower_sq(const float* __restrict__ in, TowerParams T, float* __restrict__ out, int B) {
+    static_assert(!CB || FROM_STATES, "the constant-plane bias needs the packed states");
+    constexpr int RTW = 13, NWAVES = 8, CTW = 4, CH = 4, NB = SQ_NB, nsq = NB * NB, PW = 16;
+    constexpr int PP4 = sq_image_pitch4<CH>(), CP4 = sq_image_cell4<CH>();  // position / cell pitch of the image in 16 B
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    f32x4* lds4 = (f32x4*)lds;
+    TG_STAMP(0, 6);  // kernel start (diagnostic build only)
+    const int tid = threadIdx.x;
+    const int pos0 = blockIdx.x * PW;
+    const int npos = min(PW, B - pos0);
+    const int wave = tid >> 6, lane = tid & 63;
+    const int ct = wave % CTW, rg = wave / CTW;
+    const int r16 = lane & 15, q = lane >> 4;
+    const int ch0 = ct * 16;
+    const uint32_t wlane = (uint32_t)(((ch0 + r16) * 4 + q) * 16);  // this lane's 16 B inside a chunk of weights
+    f32x4 w0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, w1 = w0;                // the weight stream's two chunks in flight between layers
+    f32x4 acc[RTW];
+    int rho0, my_tiles;
+    tower_plain_layer0<RTW, NWAVES, CH0, CH, NB, FROM_STATES, CB>(in, T, lds4, PW, pos0, npos, CTW, wlane, acc, rho0, my_tiles, w0, w1);
+    if (T.nlayers == 1) {  // no residual block: layer 0 is the tower's output
+#pragma unroll
+        for (int j = 0; j < RTW; j++) {
+            const int rho = rho0 + j * 16;
+            if (j < my_tiles && rho < npos * nsq) {
+                const int p = pos0 + rho / nsq, sq = rho % nsq;
+                if (T.frag_out) ((f32x4*)out)[((size_t)(p >> 4) * (nsq * CH) + sq * CH + ct) * 64 + (p & 15) * 4 + q] = acc[j];
+                else *(f32x4*)&out[((size_t)pos0 * nsq + rho) * (16 * CH) + ch0 + 4 * q] = acc[j];
+            }
+        }
+        return;
+    }
+    TG_STAMP(0, 2);
+    __syncthreads();  // every wave has finished reading the input planes
+    TG_STAMP(0, 3);
+    // the square-tile image replaces them.  Every cell of all PW positions is written: the rows of a ragged workgroup's missing
+    // positions read the zero row in layer 0, so their cells hold finite values (bias, ReLU) that later layers read and never store
+#pragma unroll
+    for (int j = 0; j < RTW; j++) {
+        const int rho = rho0 + j * 16;
+        if (j < my_tiles) {
+            const int p = rho / nsq, sq = rho - p * nsq;
+            lds4[p * PP4 + sq * CP4 + (ch0 >> 2) + q] = acc[j];
+        }
+        acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    TG_STAMP(0, 4);
+    __syncthreads();
+    TG_STAMP(0, 5);
+
+    // ---- layers 1 … : this lane's tile column is position r16 ----
+    int ad = r16 * PP4 + q;
+    const int turn = rg;  // waves w and w + 4 share a SIMD
+    for (int layer = 1; layer < T.nlayers; layer++) {
+        // (the address is the same in every layer, but the compiler must not know: it would hoist the (address + offset) sums of
+        // the main loop out of the layer loop and spill them instead of using ds_read immediates)
+        asm volatile("" : "+v"(ad));
+        const f32x4* img4 = lds4 + ad;
+        TG_STAMP(layer, 0);
+        const float* wnext = T.w[layer + 1 < T.nlayers ? layer + 1 : layer];
+        const f32x4 bv = *(const f32x4*)&T.b[layer][ch0 + 4 * q];  // requested here: its latency passes under the main loop
+        if (rg == 0) conv_mainloop_sq<0, CH>(img4, T.w[layer], wnext, wlane, acc, turn, w0, w1);
+        else conv_mainloop_sq<1, CH>(img4, T.w[layer], wnext, wlane, acc, turn, w0, w1);
+        TG_STAMP(layer, 1);
+#pragma unroll
+        for (int j = 0; j < RTW; j++) {
+            f32x4 v = acc[j] + bv;
+            v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
+            acc[j] = v;
+        }
+        if (layer + 1 == T.nlayers) {
+            if (r16 < npos) {
+                // (opaque to the compiler, like the image address: it would otherwise compute all 2 × 13 64-bit store addresses
+                // before the layer loop and keep them in scratch)
+                int p = pos0 + r16;
+                asm volatile("" : "+v"(p));
+                if (rg == 0) tower_sq_store<0, CH>(acc, T, out, p, q, ct);
+                else tower_sq_store<1, CH>(acc, T, out, p, q, ct);
+            }
+            break;
+        }
+        TG_STAMP(layer, 2);
+        __syncthreads();  // every wave has finished reading the previous image
+        TG_STAMP(layer, 3);
+        const bool conv1 = (layer & 1) == 1;  // next layer is conv2 of the same block: it starts from the block input
+        f32x4* cell4 = lds4 + ad + (ch0 >> 2);
+        if (rg == 0) tower_sq_writeback<0, CH>(cell4, acc, conv1);
+        else tower_sq_writeback<1, CH>(cell4, acc, conv1);
         TG_STAMP(layer, 4);
         __syncthreads();
         TG_STAMP(layer, 5);
@@ -1957,18 +2106,37 @@ static hipError_t launch_tower_halo_t(hipStream_t st, const float* in, const Tow
     return hipGetLastError();
 }
 
-// full batches of the three BASELINE topologies run on the halo image (identical bits, see k_tower_halo)
+template <int CH0, bool FROM_STATES, bool CB = false>
+static hipError_t launch_tower_sq_t(hipStream_t st, const float* in, const TowerParams& T, float* out, int B) {
+    constexpr int PW = 16, NB = SQ_NB, CH = 4;
+    const size_t plain = (size_t)(PW * NB * NB + 1) * ((CB ? T.cb_cin_pad : T.cin_pad) + LDS_PAD16) * sizeof(float) +
+                         (CB ? tower_cb_table_bytes(PW, 16 * CH) : 0);
+    const size_t image = (size_t)PW * sq_image_pitch4<CH>() * 16;  // 115 200 B
+    const size_t lds = plain > image ? plain : image;
+    static LdsAttr lds_attr;
+    if (hipError_t e = lds_attr.ensure((const void*)k_tower_sq<CH0, FROM_STATES, CB>, lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_tower_sq<CH0, FROM_STATES, CB>), dim3((B + PW - 1) / PW), dim3(512), lds, st, in, T, out, B);
+    return hipGetLastError();
+}
+
+bool tower_square_tiles(int n, int F, int B) {
+    static const bool off = env_on("TG_NO_HALO_TOWER");
+    return !off && n == SQ_NB && F == 64 && B > 2048;
+}
+
+// full batches of the three BASELINE topologies run on the halo image (identical bits, see k_tower_halo); 5×5 with 64 filters
+// on the square-tile image (k_tower_sq)
 template <bool FROM_STATES>
 static bool launch_tower_halo(hipStream_t st, const float* in, const TowerParams& T, float* out, int B, int n, hipError_t* err) {
     static const bool off = env_on("TG_NO_HALO_TOWER");
     if (off || !T.slotmap) return false;
     if (FROM_STATES && T.cb) {  // layer 0 over the board planes, constant planes as a bias (CH0 = 2)
-        if (n == 5 && T.F == 64 && B > 2048) { *err = launch_tower_halo_t<13, 8, 2, 4, 5, FROM_STATES, FROM_STATES>(st, in, T, out, B, 4); return true; }
+        if (tower_square_tiles(n, T.F, B)) { *err = launch_tower_sq_t<2, FROM_STATES, FROM_STATES>(st, in, T, out, B); return true; }
         if (n == 6 && T.F == 128 && B > 512) { *err = launch_tower_halo_t<9, 8, 2, 8, 6, FROM_STATES, FROM_STATES>(st, in, T, out, B, 8); return true; }
         if (n == 5 && T.F == 128 && B > 1024) { *err = launch_tower_halo_t<13, 8, 2, 8, 5, FROM_STATES, FROM_STATES>(st, in, T, out, B, 8); return true; }
         return false;
     }
-    if (n == 5 && T.F == 64 && T.cin_pad == 80 && B > 2048) { *err = launch_tower_halo_t<13, 8, 5, 4, 5, FROM_STATES>(st, in, T, out, B, 4); return true; }
+    if (tower_square_tiles(n, T.F, B) && T.cin_pad == 80) { *err = launch_tower_sq_t<5, FROM_STATES>(st, in, T, out, B); return true; }
     if (n == 6 && T.F == 128 && T.cin_pad == 96 && B > 512) { *err = launch_tower_halo_t<9, 8, 6, 8, 6, FROM_STATES>(st, in, T, out, B, 8); return true; }
     if (n == 5 && T.F == 128 && T.cin_pad == 80 && B > 1024) { *err = launch_tower_halo_t<13, 8, 5, 8, 5, FROM_STATES>(st, in, T, out, B, 8); return true; }
     return false;
