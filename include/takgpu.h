@@ -355,6 +355,25 @@ typedef struct TgNodeRecord {
     uint32_t q_bits;
 } TgNodeRecord;
 TG_API int tg_search_dump(TgEngine* e, int game, TgNodeRecord* records, size_t capacity, size_t* n_records);
+/* Node::debug(depth) (alpha-tak/src/search/debug.rs:9-51) of every game's root, computed on the device.
+ *   moves / visits / reward (= q) / policy (= prior): games × TG_MAX_MOVES, the root's children sorted by visits descending,
+ *     ties by child index DESCENDING (a stable ascending sort followed by reverse(); the reference's sort_unstable_by_key +
+ *     reverse gives the same order for ≤ 20 children and leaves it unspecified beyond).  counts: games.
+ *   eval: games, NodeDebugInfo::eval in f32: total = (float)(u32 sum of visits), acc = +0.0f, acc = acc + reward_i *
+ *     ((float)visits_i / total) in the sorted order, no contraction.  No children → +0.0; children but no visits → NaN.
+ *   cont_moves / cont_visits: games × top_k × depth, cont_len: games × top_k — Node::continuation(depth) of the first top_k
+ *     sorted children: while the node is initialised (visits or virtual visits ≠ 0) and has children, step to its most
+ *     visited child (the LAST one on ties, pick_move(true)) and record (move, that child's visits).
+ * Entries past counts[g] or cont_len are zero.  Any pointer may be NULL.  0 ≤ depth ≤ TG_DEBUG_MAX_DEPTH and
+ * 0 ≤ top_k ≤ TG_MAX_MOVES, else TG_ERR_INVALID_ARG.  The games run in slices whose device scratch stays within
+ * TG_DEBUG_SCRATCH_BYTES (one game needs at most ≈ 200 KB); one synchronisation per slice. */
+#define TG_DEBUG_MAX_DEPTH 64
+#define TG_DEBUG_SCRATCH_BYTES (1 << 26)
+TG_API int tg_search_debug(TgEngine* e, int depth, int top_k,
+                           TgMove* moves, uint32_t* visits, float* reward, float* policy,
+                           int32_t* counts, float* eval,
+                           TgMove* cont_moves, uint32_t* cont_visits,
+                           int32_t* cont_len);
 /* counters since tg_search_create: expansions = completed rollouts (terminal ones included,
  * as in the reference's ROLLOUTS loop), evals = leaves sent to the network */
 TG_API int tg_search_counters(TgEngine* e, uint64_t* expansions, uint64_t* evals);

@@ -203,6 +203,7 @@ hipError_t launch_sum_rows(hipStream_t st, const float* rows, int n, double* out
 // search_kernels.hip
 struct SearchDev;
 struct SelfPlayDev;
+struct DebugOut;
 void launch_select(hipStream_t st, const SearchDev& S, const uint8_t* active);
 void launch_backup(hipStream_t st, const SearchDev& S);
 void launch_backup_select(hipStream_t st, const SearchDev& S);  // backup of iteration i + select of iteration i+1 (batch 1)
@@ -211,6 +212,8 @@ void launch_apply_noise(hipStream_t st, const SearchDev& S, const uint8_t* activ
 void launch_reroot(hipStream_t st, const SearchDev& S, const int32_t* op);
 void launch_root_stats(hipStream_t st, const SearchDev& S, uint16_t* moves, uint32_t* visits, float* prior, float* q, int32_t* counts,
                        uint32_t* root_visits, float* root_q);
+// Node::debug of games [g0, g0 + games) into slice-local rows of `o` (k_search_debug)
+void launch_search_debug(hipStream_t st, const SearchDev& S, int g0, int games, int depth, int top_k, const DebugOut& o);
 void launch_play_move(hipStream_t st, const SearchDev& S, const uint16_t* moves, const uint8_t* active, int32_t* op);
 void launch_sp_opening(hipStream_t st, const SearchDev& S);
 void launch_sp_instant_win(hipStream_t st, const SearchDev& S, const SelfPlayDev& P);

@@ -109,6 +109,19 @@ struct SearchDev {
     uint64_t seed;
 };
 
+// tg_search_debug outputs of one slice of games (k_search_debug, search_kernels.hip)
+struct DebugOut {
+    uint16_t* moves;
+    uint32_t* visits;
+    float* reward;
+    float* policy;
+    int32_t* counts;
+    float* eval;
+    uint16_t* cont_moves;
+    uint32_t* cont_visits;
+    int32_t* cont_len;
+};
+
 struct SelfPlayDev {
     // staging of the current game's examples per slot
     ExampleRec* st_hdr;   // [G][ex_per_game]

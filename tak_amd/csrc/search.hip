@@ -19,6 +19,7 @@ struct Search {
     DevBuf hot, cold, root, alloc, chunk_head, chunk_link, chunk_fwd, chunk_used, free_ring, pool_ctl, root_state, alive, generation, path_len, path, leaf_kind, leaf_rec, child_pidx, child_logit, leaf_hash, planes, leaf_state, policy, eval,
         ctab, err, counters, op, active, noise, abort;
     DevBuf r_moves, r_visits, r_prior, r_q, r_counts, r_rv, r_rq, s_moves;
+    DevBuf dbg_moves, dbg_visits, dbg_reward, dbg_policy, dbg_counts, dbg_eval, dbg_cmoves, dbg_cvisits, dbg_clen;  // tg_search_debug, one slice
     // self-play
     bool selfplay = false;
     TgSelfPlayConfig spcfg;
@@ -507,6 +508,52 @@ int tg_search_root(TgEngine* e, TgMove* moves, uint32_t* visits, float* prior, f
     if (counts) TG_HIP(hipMemcpy(counts, s->r_counts.p, G * 4, hipMemcpyDeviceToHost));
     if (root_visits) TG_HIP(hipMemcpy(root_visits, s->r_rv.p, G * 4, hipMemcpyDeviceToHost));
     if (root_q) TG_HIP(hipMemcpy(root_q, s->r_rq.p, G * 4, hipMemcpyDeviceToHost));
+    return TG_OK;
+}
+
+int tg_search_debug(TgEngine* e, int depth, int top_k, TgMove* moves, uint32_t* visits, float* reward, float* policy, int32_t* counts,
+                    float* eval, TgMove* cont_moves, uint32_t* cont_visits, int32_t* cont_len) {
+    int rc = need_search(e);
+    if (rc) return rc;
+    if (depth < 0 || depth > TG_DEBUG_MAX_DEPTH || top_k < 0 || top_k > TG_MAX_MOVES)
+        return fail(TG_ERR_INVALID_ARG, "tg_search_debug: need 0 <= depth <= TG_DEBUG_MAX_DEPTH and 0 <= top_k <= TG_MAX_MOVES");
+    Search* s = e->search;
+    rc = sync_and_check(e);
+    if (rc) return rc;
+    const size_t G = (size_t)s->d.G;
+    // no continuation output wanted → walk none
+    const size_t K = (cont_moves || cont_visits || cont_len) ? (size_t)top_k : 0, D = (size_t)depth;
+    // the device scratch of one slice of games stays within TG_DEBUG_SCRATCH_BYTES (≤ 200 KB per game: at least 300 games a slice)
+    const size_t per_game = EX_MOVES * (2 + 4 + 4 + 4) + 4 + 4 + K * D * (2 + 4) + K * 4;
+    const size_t slice = std::max<size_t>(1, std::min<size_t>(G, (size_t)TG_DEBUG_SCRATCH_BYTES / per_game));
+    TG_HIP(s->dbg_moves.ensure(slice * EX_MOVES * 2));
+    TG_HIP(s->dbg_visits.ensure(slice * EX_MOVES * 4));
+    TG_HIP(s->dbg_reward.ensure(slice * EX_MOVES * 4));
+    TG_HIP(s->dbg_policy.ensure(slice * EX_MOVES * 4));
+    TG_HIP(s->dbg_counts.ensure(slice * 4));
+    TG_HIP(s->dbg_eval.ensure(slice * 4));
+    TG_HIP(s->dbg_cmoves.ensure(std::max<size_t>(1, slice * K * D * 2)));
+    TG_HIP(s->dbg_cvisits.ensure(std::max<size_t>(1, slice * K * D * 4)));
+    TG_HIP(s->dbg_clen.ensure(std::max<size_t>(1, slice * K * 4)));
+    DebugOut o{s->dbg_moves.as<uint16_t>(), s->dbg_visits.as<uint32_t>(), s->dbg_reward.as<float>(), s->dbg_policy.as<float>(),
+               s->dbg_counts.as<int32_t>(), s->dbg_eval.as<float>(), s->dbg_cmoves.as<uint16_t>(), s->dbg_cvisits.as<uint32_t>(),
+               s->dbg_clen.as<int32_t>()};
+    for (size_t g0 = 0; g0 < G; g0 += slice) {
+        const size_t ns = std::min(slice, G - g0);
+        launch_search_debug(e->stream, s->d, (int)g0, (int)ns, depth, (int)K, o);
+        TG_HIP(hipGetLastError());
+        TG_HIP(hipStreamSynchronize(e->stream));
+        const size_t R = g0 * EX_MOVES, C = g0 * K * D;
+        if (moves) TG_HIP(hipMemcpy(moves + R, o.moves, ns * EX_MOVES * 2, hipMemcpyDeviceToHost));
+        if (visits) TG_HIP(hipMemcpy(visits + R, o.visits, ns * EX_MOVES * 4, hipMemcpyDeviceToHost));
+        if (reward) TG_HIP(hipMemcpy(reward + R, o.reward, ns * EX_MOVES * 4, hipMemcpyDeviceToHost));
+        if (policy) TG_HIP(hipMemcpy(policy + R, o.policy, ns * EX_MOVES * 4, hipMemcpyDeviceToHost));
+        if (counts) TG_HIP(hipMemcpy(counts + g0, o.counts, ns * 4, hipMemcpyDeviceToHost));
+        if (eval) TG_HIP(hipMemcpy(eval + g0, o.eval, ns * 4, hipMemcpyDeviceToHost));
+        if (K * D && cont_moves) TG_HIP(hipMemcpy(cont_moves + C, o.cont_moves, ns * K * D * 2, hipMemcpyDeviceToHost));
+        if (K * D && cont_visits) TG_HIP(hipMemcpy(cont_visits + C, o.cont_visits, ns * K * D * 4, hipMemcpyDeviceToHost));
+        if (K && cont_len) TG_HIP(hipMemcpy(cont_len + g0 * K, o.cont_len, ns * K * 4, hipMemcpyDeviceToHost));
+    }
     return TG_OK;
 }
 

@@ -696,6 +696,103 @@ __global__ __launch_bounds__(64) void k_root_stats(SearchDev S, uint16_t* moves,
     }
 }
 
+// tg_search_debug: Node::debug(depth) of every root (alpha-tak/src/search/debug.rs:9-51), one 256-thread workgroup per game of the
+// slice [g0, g0 + gridDim.x).  Outputs are slice-local (row b = game g0 + b):
+//   children  [b][EX_MOVES]      sorted by visits descending, ties by child index descending (a stable ascending sort + reverse();
+//                                the reference's sort_unstable_by_key + reverse gives the same for ≤ 20 children, leaves it
+//                                unspecified beyond); zero past the child count
+//   counts/eval [b]              eval = Σ reward_i · (visits_i / total) in the sorted order from +0.0f, f32, no contraction
+//   cont_*    [b][top_k][depth]  Node::continuation of the first top_k sorted children: while the node is initialised (visits or
+//                                virtual visits ≠ 0) and has children, step to its most visited child (last on ties, pick_move(true),
+//                                play.rs:49-57); zero past cont_len [b][top_k]
+// Every index read from the tree is checked against the pool (a bad one ends that walk), so no read leaves the node arrays.
+constexpr int DBG_WAVES = 4;
+
+__global__ __launch_bounds__(DBG_WAVES * 64) void k_search_debug(SearchDev S, int g0, int depth, int top_k, DebugOut o) {
+    __shared__ uint64_t key[EX_MOVES];     // (visits << 32) | child index, in child order
+    __shared__ uint32_t s_node[EX_MOVES];  // sorted position → pool index of the child
+    __shared__ uint32_t s_vis[EX_MOVES];
+    __shared__ float s_q[EX_MOVES];
+    const int b = blockIdx.x, g = g0 + b;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t pool = (uint64_t)S.n_chunks << S.chunk_shift;
+    const uint32_t root = S.root[g];
+    uint32_t nchild = 0, cb = 0;
+    if (root < pool) {
+        const NodeCold rc = S.cold[root];
+        nchild = min((uint32_t)rc.nres & 0xfffu, (uint32_t)EX_MOVES);
+        cb = rc.child;
+        if ((uint64_t)cb + nchild > pool) nchild = 0;
+    }
+    for (uint32_t i = tid; i < nchild; i += DBG_WAVES * 64) key[i] = ((uint64_t)S.hot[cb + i].visits << 32) | i;
+    __syncthreads();
+    // rank = number of children with a larger key (all keys differ): the child's position in the sorted list
+    for (uint32_t i = tid; i < (uint32_t)EX_MOVES; i += DBG_WAVES * 64) {
+        const size_t ob = (size_t)b * EX_MOVES;
+        if (i < nchild) {
+            const uint64_t ki = key[i];
+            uint32_t r = 0;
+            for (uint32_t j = 0; j < nchild; j++) r += key[j] > ki ? 1u : 0u;
+            const NodeHot h = S.hot[cb + i];
+            o.moves[ob + r] = S.cold[cb + i].mv;
+            o.visits[ob + r] = h.visits;
+            o.reward[ob + r] = h.q;
+            o.policy[ob + r] = h.prior;
+            s_node[r] = cb + i;
+            s_vis[r] = h.visits;
+            s_q[r] = h.q;
+        } else {  // the ranks of the children fill [0, nchild) exactly
+            o.moves[ob + i] = 0;
+            o.visits[ob + i] = 0;
+            o.reward[ob + i] = 0.0f;
+            o.policy[ob + i] = 0.0f;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {  // NodeDebugInfo::eval (debug.rs:43-51): u32 sum of visits, then one f32 chain in the sorted order
+        uint32_t sum = 0;
+        for (uint32_t r = 0; r < nchild; r++) sum += s_vis[r];
+        const float total = (float)sum;
+        float acc = 0.0f;
+        for (uint32_t r = 0; r < nchild; r++) acc = acc + s_q[r] * ((float)s_vis[r] / total);
+        o.counts[b] = (int32_t)nchild;
+        o.eval[b] = acc;
+    }
+    // continuations: wave w walks ranks r ≡ w (mod DBG_WAVES); each level is one coalesced scan of the node's children
+    for (int r = wave; r < top_k; r += DBG_WAVES) {
+        const size_t ob = ((size_t)b * top_k + r) * depth;
+        int len = 0;
+        uint32_t node = (uint32_t)r < nchild ? s_node[r] : 0u;
+        while ((uint32_t)r < nchild && len < depth) {
+            const NodeHot h = S.hot[node];
+            const NodeCold c = S.cold[node];
+            const uint32_t nch = (uint32_t)c.nres & 0xfffu, ccb = c.child;
+            if ((h.visits == 0 && h.virt == 0) || nch == 0 || (uint64_t)ccb + nch > pool) break;
+            uint64_t best = 0;
+            for (uint32_t i = lane; i < nch; i += 64) {
+                const uint64_t k = ((uint64_t)S.hot[ccb + i].visits << 32) | i;
+                best = k > best ? k : best;
+            }
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                const uint64_t ot = __shfl_xor(best, d);
+                best = ot > best ? ot : best;
+            }
+            node = ccb + (uint32_t)best;
+            if (lane == 0) {
+                o.cont_moves[ob + len] = S.cold[node].mv;
+                o.cont_visits[ob + len] = (uint32_t)(best >> 32);
+            }
+            len++;
+        }
+        for (int l = len + lane; l < depth; l += 64) {
+            o.cont_moves[ob + l] = 0;
+            o.cont_visits[ob + l] = 0;
+        }
+        if (lane == 0) o.cont_len[(size_t)b * top_k + r] = len;
+    }
+}
+
 // tg_search_play: find the child for a caller-chosen move, play it on the root state
 __global__ __launch_bounds__(WPB * 64) void k_play_move(SearchDev S, const uint16_t* __restrict__ moves, const uint8_t* __restrict__ active,
                                                    int32_t* __restrict__ op) {
@@ -1022,6 +1119,9 @@ void launch_reroot(hipStream_t st, const SearchDev& S, const int32_t* op) {
 void launch_root_stats(hipStream_t st, const SearchDev& S, uint16_t* moves, uint32_t* visits, float* prior, float* q, int32_t* counts,
                        uint32_t* root_visits, float* root_q) {
     hipLaunchKernelGGL(k_root_stats, dim3(S.G), dim3(64), 0, st, S, moves, visits, prior, q, counts, root_visits, root_q);
+}
+void launch_search_debug(hipStream_t st, const SearchDev& S, int g0, int games, int depth, int top_k, const DebugOut& o) {
+    hipLaunchKernelGGL(k_search_debug, dim3(games), dim3(DBG_WAVES * 64), 0, st, S, g0, depth, top_k, o);
 }
 void launch_play_move(hipStream_t st, const SearchDev& S, const uint16_t* moves, const uint8_t* active, int32_t* op) {
     hipLaunchKernelGGL(k_play_move, wgrid(S.G), dim3(WPB * 64), 0, st, S, moves, active, op);

@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("TAKGPU_LIB") or os.path.join(_HERE, "libtakgpu.so")  
 
 TG_ABI_VERSION = 5
 TG_MAX_MOVES = 512
+TG_DEBUG_MAX_DEPTH = 64
 HEAD_FC5, HEAD_CONV = 0, 1
 EVAL_RESNET, EVAL_DUMMY, EVAL_HASH = 0, 1, 2
 
@@ -109,7 +110,7 @@ ABI_SYMBOLS = [
     "tg_input_channels", "tg_policy_size", "tg_movegen", "tg_play", "tg_result", "tg_encode", "tg_move_index",
     "tg_perft", "tg_net_set_tensor", "tg_net_init_random", "tg_net_get_tensor", "tg_net_finalize", "tg_net_set_precision", "tg_policy_eval", "tg_forward_mcts", "tg_policy_eval_dev",
     "tg_search_create", "tg_search_reset", "tg_search_run", "tg_search_apply_dirichlet", "tg_search_apply_noise",
-    "tg_search_root", "tg_search_play", "tg_search_states", "tg_search_dump", "tg_search_counters", "tg_search_pool",
+    "tg_search_root", "tg_search_play", "tg_search_states", "tg_search_dump", "tg_search_debug", "tg_search_counters", "tg_search_pool",
     "tg_selfplay_create", "tg_selfplay_step", "tg_selfplay_stats", "tg_selfplay_drain",
     "tg_profile_enable", "tg_profile_read", "tg_board_pass_bench",
     "tg_augment_examples",
@@ -647,6 +648,25 @@ class Engine:
         nrec = C.c_size_t(0)
         self._check(self.lib.tg_search_dump(self.h, game, _p(rec), C.c_size_t(capacity), C.byref(nrec)))
         return rec[: nrec.value].copy()
+
+    def search_debug(self, depth=10, top_k=TG_MAX_MOVES):
+        """Node::debug(depth) of every root (tg_search_debug): children sorted by visits (ties: higher child index first), eval, and
+        the continuations of the first top_k sorted children.  Arrays are zero past counts / cont_len."""
+        g = self.games
+        moves = np.zeros((g, TG_MAX_MOVES), np.uint16)
+        visits = np.zeros((g, TG_MAX_MOVES), np.uint32)
+        reward = np.zeros((g, TG_MAX_MOVES), np.float32)
+        policy = np.zeros((g, TG_MAX_MOVES), np.float32)
+        counts = np.zeros(g, np.int32)
+        ev = np.zeros(g, np.float32)
+        k, d = max(int(top_k), 0), max(int(depth), 0)
+        cont_moves = np.zeros((g, k, d), np.uint16)
+        cont_visits = np.zeros((g, k, d), np.uint32)
+        cont_len = np.zeros((g, k), np.int32)
+        self._check(self.lib.tg_search_debug(self.h, int(depth), int(top_k), _p(moves), _p(visits), _p(reward), _p(policy), _p(counts),
+                                             _p(ev), _p(cont_moves), _p(cont_visits), _p(cont_len)))
+        return dict(moves=moves, visits=visits, reward=reward, policy=policy, counts=counts, eval=ev, cont_moves=cont_moves,
+                    cont_visits=cont_visits, cont_len=cont_len)
 
     def search_counters(self):
         a, b = C.c_uint64(0), C.c_uint64(0)

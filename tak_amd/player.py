@@ -1,5 +1,5 @@
 """`Player` (reference alpha-tak/src/player.rs:22-199) on top of the engine's search entry points — the API shape bots and
-the analysis tools use for ONE game: rollout / add_noise / pick_move / play_move / get_examples.
+the analysis tools use for ONE game: rollout / add_noise / pick_move / play_move / get_examples / debug / get_analysis.
 
 The reference overlaps a rollout thread with the network call (one batch of virtual rollouts always in flight).  Here the
 tree lives on the GPU and `rollout` is one iteration of the one-game search with TgSearchConfig.batch = `batch`: `batch` virtual
@@ -8,16 +8,22 @@ updates as Player::rollout (player.rs:77-110, 125-128), without the thread.  The
 Players can share one engine only one at a time (the engine holds one search state)."""
 import numpy as np
 
+from .analysis import MAX_BRANCH_LENGTH, Analysis, NodeDebugInfo
 from .engine import TG_MAX_MOVES
 
 
 class Player:
-    def __init__(self, engine, batch, save_examples, game, arena_nodes=1 << 16, seed=0):
-        """Player::new(network, batch, save_examples, create_analysis = false, &game); `game` is a packed state."""
+    def __init__(self, engine, batch, save_examples, game, arena_nodes=1 << 16, seed=0, create_analysis=False):
+        """Player::new(network, batch, save_examples, create_analysis, &game); `game` is a packed state."""
         self.e = engine
         self.batch = int(batch)
         self.save_examples = bool(save_examples)
+        self.create_analysis = bool(create_analysis)
         self.examples = []  # IncompleteExample: (state, moves, visits)
+        game = np.ascontiguousarray(game, np.uint8).reshape(-1)
+        # Analysis::new(N, game.half_komi, game.ply) (player.rs:58) from the packed header (TgHeader: ply u16 at 2, half_komi i8 at 8)
+        hdr = game[engine.sb - 16:]
+        self.analysis = Analysis(engine.n, int(hdr[8:9].view(np.int8)[0]), int(hdr[2:4].view("<u2")[0]))
         self.rng = np.random.default_rng(seed)
         engine.search_create(1, arena_nodes=arena_nodes, seed=seed, batch=self.batch)
         engine.search_reset(np.ascontiguousarray(game, np.uint8).reshape(1, -1))
@@ -52,13 +58,28 @@ class Player:
             raise RuntimeError("pick_move: no visits to sample from")  # WeightedIndex panics in the reference
         return int(moves[int(self.rng.choice(len(moves), p=visits / total))])
 
+    def debug(self, depth):
+        """Node::debug(depth) of the root (player.rs:113-115): one tg_search_debug call, every child's continuation"""
+        r = self.e.search_debug(depth, TG_MAX_MOVES)
+        return NodeDebugInfo.from_search_debug(self.e.n, r, 0)
+
     def play_move(self, move, game=None, with_info=True):
-        """Advance the tree (tree reuse) and the game; record an IncompleteExample (player.rs:136-166)."""
+        """Advance the tree (tree reuse) and the game; record an IncompleteExample and update the analysis (player.rs:136-166)."""
         if self.save_examples and with_info:
             moves, visits = self.improved_policy()
             self.examples.append((self.state().copy(), moves, visits))
+        if self.create_analysis:
+            if with_info:
+                self.analysis.update(self.debug(MAX_BRANCH_LENGTH), move)
+            else:
+                self.analysis.add_move_without_info(move)
         self.e.search_play(np.array([move], np.uint16))
         self.rollout()  # refill: the new root is expanded like the batch the reference keeps in flight
+
+    def get_analysis(self):
+        """the game's Analysis (player.rs:196-198); like std::mem::take the Player keeps an empty default one"""
+        a, self.analysis = self.analysis, Analysis.default(self.e.n)
+        return a
 
     def get_examples(self, result):
         """Complete the collected examples with the game result (TgResult code) from each mover's perspective
