@@ -630,8 +630,8 @@ TG_API int tg_board_pass_bench(TgEngine* e, int n, const void* states, const TgM
 TG_API int tg_profile_read(TgEngine* e, TgProfile* out);     /* synchronises; resets the totals */
 
 /* A/B switches.  The library reads a fixed set of TG_* environment variables (every one is read through ONE
- * function: a switch is on when the variable is set to anything but "" or "0"; the two numeric ones — TG_TOWER_VARIANT,
- * TG_WGRAD_PW — take their value, 0 = off).  tg_debug_switches writes the switches that are ON in this process's
+ * function: a switch is on when the variable is set to anything but "" or "0"; the numeric one, TG_WGRAD_PW, takes its
+ * value, 0 = off).  tg_debug_switches writes the switches that are ON in this process's
  * environment as "NAME=value NAME=value …" into buf (always NUL-terminated, truncated to cap) and returns their number:
  * 0 on a measured run — bench.py prints the list as config.switches_set.  Needs no engine and no GPU. */
 TG_API int tg_debug_switches(char* buf, size_t cap);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B timing of the network forward (tower + heads) on one BASELINE topology: `python scripts/ab_forward.py [c2|c3|c5]`.
-Kernel variants are selected through environment variables read by the launchers (e.g. TG_TOWER_VARIANT); prints the
+Kernel variants are selected through environment variables read by the launchers (e.g. TG_NO_HALO_TOWER); prints the
 forward time and, from the in-library HIP-event profile, the tower's launch time."""
 import json
 import os

@@ -61,8 +61,6 @@ struct TgEngine {
     TgConfig cfg;
     tg::Geom g;
     hipStream_t stream = nullptr;
-    hipStream_t half_stream[2] = {nullptr, nullptr};  // dual-stream rollouts (search.hip)
-    hipEvent_t half_event[3] = {nullptr, nullptr, nullptr};
     int cin = 0;          // input channels
     int cin_pad = 0;      // channels per NHWC input row (multiple of 16, zero padded)
     int policy_size = 0;  // P
@@ -99,9 +97,6 @@ const float* net_fc_stats(const TgEngine* e, int* blocks, int* stride);  // bloc
 bool net_gather_ok(const TgEngine* e, int leaves);          // will a logits-only forward of `leaves` rows write the children's logits (net_set_gather)?
 void net_set_gather(TgEngine* e, const FcGatherArgs* g);    // the search's child_pidx / leaf_rec / child_logit buffers, or nullptr
 const float* net_fc_logits(const TgEngine* e, int* ld);  // FC head: logits buffer for logits-only forwards (d_policy = nullptr), else nullptr
-int net_forward_states_at(TgEngine* e, int n, const uint8_t* d_states, float* d_policy, float* d_eval, hipStream_t st, int pos0);
-bool net_profile_due(const TgEngine* e);
-void net_profile_skip(TgEngine* e);
 const std::map<std::string, std::vector<float>>* net_tensors(const TgEngine* e);  // tensors as given to tg_net_set_tensor
 // train.hip
 void trainer_destroy(Trainer* t);

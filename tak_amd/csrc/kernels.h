@@ -126,13 +126,13 @@ struct TowerS3Params {
 // positions per workgroup and position stride of the split tower's halo image
 bool tower_s3_halo_geometry(int n, int F, int* pw, int* ps);
 bool tower_s3_supported(int n, int F);
-// out_split: write the final activations in the split row layout (per 8 channels 16 B hi, 16 B lo) for k_fc_s3
+// out_split: write the final activations in the split row layout (per 8 channels 16 B hi, 16 B lo) for the split FC
 hipError_t launch_tower_s3(hipStream_t st, const float* planes, const TowerS3Params& T, float* out, int B, int n, bool out_split);
 hipError_t launch_tower_s3_states(hipStream_t st, const uint8_t* states, const TowerS3Params& T, float* out, int B, int n, bool out_split);
+constexpr int FC_S3_COLS = 112;  // outputs per column block of the split FC (k_fc_s3b) and of its weight layout
 bool fc_s3_supported(int K, int NP);
-int fc_s3_cols(int NP);
-// Wp: [chunk of 32 k][NP/208 column blocks][q][hi|lo][208 outputs][8 bf16], k = sq·F + c
-// stats (optional, NP % 112 == 0): block-wise softmax statistics over columns < n_soft, [M][NP/112][2] (softmax.cuh)
+// Wp: [chunk of 32 k][NP/112 column blocks][q][hi|lo][112 outputs][8 bf16], k = sq·F + c
+// stats (optional): block-wise softmax statistics over columns < n_soft, [M][FC_STAT_STRIDE][2] (softmax.cuh)
 struct FcGatherArgs;
 hipError_t launch_fc_s3(hipStream_t st, const float* act_split, const void* Wp, const void* Wr, const float* bias, float* out, int M, int K, int NP,
                         int out_stride, int n_valid, float* stats = nullptr, int n_soft = 0, const FcGatherArgs* gather = nullptr);

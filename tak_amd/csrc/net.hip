@@ -52,7 +52,6 @@ struct Net {
     DevBuf split_ctl;                  // k_tower_split: a counter line per position, then the error word a bounded wait raises (TOWER_SPLIT_CTL_WORDS)
     DevBuf split_buf;                  // k_tower_split: two exchange buffers of TOWER_SPLIT_MAX_BATCH positions × n² × F floats
     DevBuf s3_halo_map;                // the same for the split tower's workgroup (k_tower_s3_halo)
-    size_t logit_row = 0;              // floats per position in `logits`
     int precision = TG_PRECISION_F32;  // tg_net_set_precision
     bool s3 = false;                   // split-bf16 tower in use
     TowerS3Params tower_s3;
@@ -277,7 +276,7 @@ int net_finalize(TgEngine* e) {
             auto wv = find(n, "value.weight", K, err);
             auto bv = wv ? find(n, "value.bias", 1, err) : nullptr;
             if (!bv) return fail(TG_ERR_WEIGHTS, err);
-            if (NP > P && !env_on("TG_SEPARATE_VALUE_HEAD")) {
+            if (NP > P) {
                 bp[P] = (*bv)[0];
                 for (int c = 0; c < F; c++)
                     for (int sq = 0; sq < nsq; sq++) {
@@ -317,14 +316,14 @@ int net_finalize(TgEngine* e) {
         TG_HIP(n->value_w.ensure(K * 4));
         TG_HIP(hipMemcpy(n->value_w.p, wv.data(), K * 4, hipMemcpyHostToDevice));
     }
-    n->fused = tower_supported(e->g.n, F, n->cin_pad) && 1 + 2 * R <= 48 && !env_on("TG_NO_FUSED_TOWER");
+    n->fused = tower_supported(e->g.n, F, n->cin_pad) && 1 + 2 * R <= 48;
     if (n->fused) {
         TowerParams& T = n->tower;
         T.nlayers = 1 + 2 * R; T.cin_pad = n->cin_pad; T.F = F;
         // layer 0: 72 of 80 (5×5) / 92 of 96 (6×6) input channels are real; with the last chunk permuted 2 of 20 / 1 of 24
         // MFMAs per tile and tap multiply padding only and are skipped — the towers get their own copy of the weights
         const int tail = n->cin - (n->cin_pad - 16);
-        T.cin_last_t = (tail > 0 && tail <= 12 && !env_on("TG_NO_CIN_PERM")) ? (tail + 3) / 4 : 4;
+        T.cin_last_t = (tail > 0 && tail <= 12) ? (tail + 3) / 4 : 4;
         if (T.cin_last_t < 2) T.cin_last_t = 4;
         {
             Folded f0;
@@ -439,19 +438,18 @@ int net_finalize(TgEngine* e) {
         n->s3_fc_on = false;
         T.head_w = nullptr; T.head_b = nullptr; T.head_out = nullptr; T.head_cout = 0;
         n->s3_head_on = false;
-        if (e->cfg.policy_head == TG_HEAD_CONV && n->policy_conv.cout_pad % 32 == 0 && !env_on("TG_S3_NO_HEAD")) {
+        if (e->cfg.policy_head == TG_HEAD_CONV && n->policy_conv.cout_pad % 32 == 0) {
             const int ch = P / nsq;
             if (!fold_conv_bn(n, "policy", "", ch, F, g, err)) return fail(TG_ERR_WEIGHTS, err);
             TG_HIP(upload_conv_s3(g, ch, F, F / 32, n->s3_head, n->policy_conv.cout_pad));
             T.head_w = n->s3_head.p; T.head_b = n->policy_conv.b.as<float>(); T.head_cout = n->policy_conv.cout_pad;
             n->s3_head_on = true;
         }
-        const int s3np = round_up(P, 112);  // column blocks of 112 outputs (k_fc_s3b); TG_S3_FC_WIDE=1 keeps the 208-wide kernel
-        n->s3_np = env_on("TG_S3_FC_WIDE") ? n->policy_np : s3np;
+        n->s3_np = round_up(P, FC_S3_COLS);
         if (e->cfg.policy_head == TG_HEAD_FC5 && fc_s3_supported(F * nsq, n->s3_np)) {
             // Linear [P, F·nsq] → split bf16 fragments, k = sq·F + c (the order of the activations)
             const size_t K = (size_t)F * nsq;
-            const int NP = n->s3_np, CB = fc_s3_cols(NP);
+            const int NP = n->s3_np, CB = FC_S3_COLS;
             auto w = find(n, "policy.weight", (size_t)P * K, err);
             auto bsrc = w ? find(n, "policy.bias", P, err) : nullptr;
             if (!bsrc) return fail(TG_ERR_WEIGHTS, err);
@@ -461,7 +459,7 @@ int net_finalize(TgEngine* e) {
                     int sq = (int)(k / F), c = (int)(k % F);
                     float v = (*w)[(size_t)o * K + (size_t)c * nsq + sq];
                     uint16_t hi = f32_to_bf16(v), lo = f32_to_bf16(v - bf16_to_f32(hi));
-                    // [chunk][column block][q][hi|lo][column][8 bf16]: the LDS plane layout of k_fc_s3 / k_fc_s3b
+                    // [chunk][column block][q][hi|lo][column][8 bf16]: the LDS plane layout of k_fc_s3b
                     const size_t cb = (size_t)o / CB, col = (size_t)o % CB, q = (k & 31) >> 3;
                     size_t slot = ((((k >> 5) * (size_t)(NP / CB) + cb) * 4 + q) * 2) * CB + col;
                     ws[slot * 8 + (k & 7)] = hi;
@@ -518,7 +516,6 @@ int net_finalize(TgEngine* e) {
     TG_HIP(n->x.ensure(((mb + 15) / 16 * 16) * nsq * F * 4));  // (whole tiles of 16 positions: fragment-major FC input)
     TG_HIP(n->y.ensure(mb * nsq * F * 4));
     size_t logit_row = e->cfg.policy_head == TG_HEAD_CONV ? (size_t)nsq * n->policy_conv.cout_pad : (size_t)std::max(n->policy_np, n->s3_np);
-    n->logit_row = logit_row;
     TG_HIP(n->logits.ensure(mb * logit_row * 4));
     TG_HIP(n->planes_nhwc.ensure(mb * nsq * n->cin_pad * 4));
     // f32 FC head with the value column: the FC emits the softmax statistics per column block, nobody re-reads whole rows
@@ -534,8 +531,7 @@ int net_finalize(TgEngine* e) {
     return TG_OK;
 }
 
-static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const uint8_t* d_states, float* d_policy, float* d_eval,
-                            hipStream_t st = nullptr, int pos0 = 0);
+static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const uint8_t* d_states, float* d_policy, float* d_eval);
 
 // planes NHWC [nb][nsq][cin_pad] (device) → policy [nb][P] (softmax, reference order), eval [nb]
 int net_forward_dev(TgEngine* e, int nb, const float* d_planes, float* d_policy, float* d_eval) {
@@ -583,19 +579,6 @@ void net_set_gather(TgEngine* e, const FcGatherArgs* g) {
     if (g) e->net->gather = *g;
 }
 
-// half batch on its own stream (only when the tower encodes from states); see search.hip
-int net_forward_states_at(TgEngine* e, int nb, const uint8_t* d_states, float* d_policy, float* d_eval, hipStream_t st, int pos0) {
-    if (!net_takes_states(e)) return fail(TG_ERR_STATE, "net_forward_states_at needs the fused tower");
-    return net_forward_impl(e, nb, nullptr, d_states, d_policy, d_eval, st, pos0);
-}
-// true when the next forward will be sampled by the profiler (it must then run alone on the GPU to be timed)
-bool net_profile_due(const TgEngine* e) {
-    const Net* n = e->net;
-    return n && n->prof_every > 0 && (n->prof_counter % (uint64_t)n->prof_every) == 0;
-}
-// a forward that was not sampled still advances the sampling counter
-void net_profile_skip(TgEngine* e) { if (e->net && e->net->prof_every > 0) e->net->prof_counter++; }
-
 int net_forward_states_dev(TgEngine* e, int nb, const uint8_t* d_states, float* d_policy, float* d_eval) {
     if (!net_ready(e)) return fail(TG_ERR_STATE, "network weights not finalized (tg_net_finalize)");
     if (nb <= 0) return TG_OK;
@@ -605,21 +588,19 @@ int net_forward_states_dev(TgEngine* e, int nb, const uint8_t* d_states, float* 
     return net_forward_impl(e, nb, e->net->planes_nhwc.as<float>(), nullptr, d_policy, d_eval);
 }
 
-// st / pos0: the stream to launch on (default: the engine stream) and the first position slot of the activation buffers
-// to use — two half batches on two streams work on disjoint slices of the same buffers (search.hip, dual-stream rollouts)
-static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const uint8_t* d_states, float* d_policy, float* d_eval,
-                            hipStream_t st, int pos0) {
+// every launch on the engine stream, the batch in the first nb position slots of the activation buffers
+static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const uint8_t* d_states, float* d_policy, float* d_eval) {
     if (!net_ready(e)) return fail(TG_ERR_STATE, "network weights not finalized (tg_net_finalize)");
     if (nb <= 0) return TG_OK;
-    if (pos0 < 0 || pos0 + nb > e->cfg.max_batch) return fail(TG_ERR_INVALID_ARG, "batch larger than max_batch");
+    if (nb > e->cfg.max_batch) return fail(TG_ERR_INVALID_ARG, "batch larger than max_batch");
     Net* n = e->net;
-    if (!st) st = e->stream;
+    hipStream_t st = e->stream;
     const int F = n->F, nsq = e->g.nsq, N = e->g.n;
     const int M = nb * nsq;
-    float* x = n->x.as<float>() + (size_t)pos0 * nsq * F;
-    float* y = n->y.as<float>() + (size_t)pos0 * nsq * F;
+    float* x = n->x.as<float>();
+    float* y = n->y.as<float>();
     std::vector<hipEvent_t>* chain = nullptr;
-    if (st == e->stream && n->prof_every > 0 && (n->prof_counter++ % (uint64_t)n->prof_every) == 0) {
+    if (n->prof_every > 0 && (n->prof_counter++ % (uint64_t)n->prof_every) == 0) {
         if (n->ev_chains.size() >= 256) {  // bound the number of pending events
             TG_HIP(hipStreamSynchronize(st));
             prof_collect(n);
@@ -642,15 +623,14 @@ static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const ui
         if (chain) chain->push_back(prof_event(n, st));
         const bool split_out = n->s3_fc_on || n->s3_head_on;
         TowerS3Params T3 = n->tower_s3;
-        if (n->s3_head_on) T3.head_out = n->logits.as<float>() + (size_t)pos0 * n->logit_row;
+        if (n->s3_head_on) T3.head_out = n->logits.as<float>();
         if (d_states) TG_HIP(launch_tower_s3_states(st, d_states, T3, x, nb, N, split_out));
         else TG_HIP(launch_tower_s3(st, d_planes, T3, x, nb, N, split_out));
         if (chain) chain->push_back(prof_event(n, st));
     } else if (n->fused) {
         if (chain) chain->push_back(prof_event(n, st));
-        // (small batches of wide networks run split by channel tile through the exchange buffers; they and the position counters
-        // belong to the engine stream's launches)
-        if (d_states) TG_HIP(launch_tower_states(st, d_states, n->tower, x, nb, N, st == e->stream ? n->split_buf.as<float>() : nullptr));
+        // (small batches of wide networks run split by channel tile through the exchange buffers)
+        if (d_states) TG_HIP(launch_tower_states(st, d_states, n->tower, x, nb, N, n->split_buf.as<float>()));
         else TG_HIP(launch_tower(st, d_planes, n->tower, x, nb, N));
         if (chain) chain->push_back(prof_event(n, st));
     } else {
@@ -666,7 +646,7 @@ static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const ui
             if (chain) chain->push_back(prof_event(n, st));
         }
     }
-    float* logits = n->logits.as<float>() + (size_t)pos0 * n->logit_row;
+    float* logits = n->logits.as<float>();
     bool value_done = false;
     if (e->cfg.policy_head == TG_HEAD_CONV) {
         const ConvLayer& L = n->policy_conv;
@@ -677,15 +657,15 @@ static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const ui
         const bool plain_value = !(n->s3 && (n->s3_fc_on || n->s3_head_on));
         TG_HIP(launch_softmax(st, logits, nsq * L.cout_pad, true, nsq, L.cout_pad, e->policy_size, nb, d_policy, nullptr, plain_value ? &vh : nullptr, &value_done));
     } else if (n->s3 && n->s3_fc_on) {
-        float* stats = n->fc_stats_on ? n->fc_stats.as<float>() + (size_t)pos0 * n->fc_stat_stride * 2 : nullptr;
-        const bool gather = !d_policy && pos0 == 0 && n->gather_on && net_gather_ok(e, nb);
+        float* stats = n->fc_stats_on ? n->fc_stats.as<float>() : nullptr;
+        const bool gather = !d_policy && n->gather_on && net_gather_ok(e, nb);
         TG_HIP(launch_fc_s3(st, x, n->s3_fc.p, n->s3_fc_ring_on ? n->s3_fc_ring.p : nullptr, n->s3_fc_b.as<float>(), logits, nb, nsq * F, n->s3_np, n->s3_np,
                             e->policy_size + (n->value_in_fc ? 1 : 0), stats, e->policy_size, gather ? &n->gather : nullptr));
         if (d_policy && stats) TG_HIP(launch_softmax_stats(st, logits, n->s3_np, stats, n->fc_stat_blocks, n->fc_stat_stride, e->policy_size, nb, d_policy, d_eval));
         else if (d_policy) TG_HIP(launch_softmax(st, logits, n->s3_np, false, nsq, 0, e->policy_size, nb, d_policy, n->value_in_fc ? d_eval : nullptr));
     } else {
-        float* stats = n->fc_stats_on ? n->fc_stats.as<float>() + (size_t)pos0 * n->fc_stat_stride * 2 : nullptr;
-        const bool gather = !d_policy && pos0 == 0 && n->gather_on && net_gather_ok(e, nb);
+        float* stats = n->fc_stats_on ? n->fc_stats.as<float>() : nullptr;
+        const bool gather = !d_policy && n->gather_on && net_gather_ok(e, nb);
         static const bool lin_src = !env_on("TG_FC_PERMUTED_SRC");  // A/B: the ring's LDS-DMA reads the [chunk][column][q] layout (same bits)
         TG_HIP(launch_gemm(st, x, nsq * F, n->policy_w.as<float>(), n->policy_b.as<float>(), logits, nb, nsq * F, n->policy_np,
                            n->policy_np, e->policy_size + (n->value_in_fc ? 1 : 0), !n->s3 && n->fused && n->tower.frag_out,

@@ -1933,6 +1933,43 @@ static hipError_t launch_conv_pos_t(hipStream_t st, const float* in, const float
     return hipGetLastError();
 }
 
+// Whole-position tilings of k_conv_pos and k_tower: RTW row tiles per wave, NWAVES waves, PW positions and CTW channel tiles per
+// workgroup, for the table of N×N boards with F channels.  A workgroup's run time is that of its positions' row tiles, whatever the
+// batch: with 16 positions per workgroup a 32-position call (the reference's BATCH_SIZE) ran 2 workgroups for as long as 4096
+// positions take.  Small batches therefore take fewer positions per workgroup; the per-element arithmetic — taps, chunks, MFMA
+// k-steps in the same order — does not depend on the tiling, so results are bit-identical.
+template <int N_, int F_, int RTW_, int NWAVES_, int PW_, int CTW_>
+struct PosTiling {
+    static constexpr int N = N_, F = F_, RTW = RTW_, NWAVES = NWAVES_, PW = PW_, CTW = CTW_;
+};
+
+// launch(PosTiling<…>{}) for B positions of the (n, F) table: 5×5 with 64 or 128, 6×6 with 128
+template <class Launch>
+static hipError_t launch_pos_tiled(int n, int F, int B, Launch&& launch) {
+    if (n == 5 && F == 64) {  // 16 positions = 25 row tiles, 4 channel tiles × 2 row groups of 13
+        // (round 6, measured at 300 … 2048 positions with 1 / 2 / 4 / 8 positions per workgroup: these brackets are within 11 % of the
+        // best choice everywhere — two co-resident workgroups of half the size take as long as one; eight waves instead of four: 5 %;
+        // every layer streaming the same L2-hot weights: no difference — profiles/r06_e_tower_pw_sweep.txt)
+        if (B <= 256) return launch(PosTiling<5, 64, 2, 4, 1, 4>{});
+        if (B <= 512) return launch(PosTiling<5, 64, 4, 4, 2, 4>{});
+        if (B <= 1024) return launch(PosTiling<5, 64, 7, 4, 4, 4>{});
+        if (B <= 2048) return launch(PosTiling<5, 64, 13, 4, 8, 4>{});
+        return launch(PosTiling<5, 64, 13, 8, 16, 4>{});
+    }
+    if (n == 6 && F == 128) {  // 4 positions = 9 row tiles, 8 channel tiles
+        if (B <= 256) return launch(PosTiling<6, 128, 3, 8, 1, 8>{});
+        if (B <= 512) return launch(PosTiling<6, 128, 5, 8, 2, 8>{});
+        return launch(PosTiling<6, 128, 9, 8, 4, 8>{});
+    }
+    if (n == 5 && F == 128) {  // 8 positions = 200 rows in 13 row tiles, 8 channel tiles
+        if (B <= 256) return launch(PosTiling<5, 128, 2, 8, 1, 8>{});
+        if (B <= 512) return launch(PosTiling<5, 128, 4, 8, 2, 8>{});
+        if (B <= 1024) return launch(PosTiling<5, 128, 7, 8, 4, 8>{});
+        return launch(PosTiling<5, 128, 13, 8, 8, 8>{});
+    }
+    return hipErrorInvalidValue;
+}
+
 // slot table of the halo image for (n, F) on the current device, built on first use (launch_conv3x3's halo path; the fused
 // tower carries its own copy in TowerParams)
 static const uint32_t* conv_halo_slotmap(int n, int F, int pw, int ps) {
@@ -1999,29 +2036,14 @@ hipError_t launch_conv3x3(hipStream_t st, const float* in, const float* Wp, cons
             return hipGetLastError();
         }
     }
-    // whole-positions kernel where the shape divides evenly (the BASELINE configs); generic tiles otherwise
-    // small batches take fewer positions per workgroup (shorter critical path, same bits — see launch_tower)
-#define TG_CONV_POS(RTW, NW, PW, CTW) \
-    return launch_conv_pos_t<RTW, NW>(st, in, Wp, bias, res, out, B, n, Cpad, CoutP, out_stride, cout_valid, relu, PW, CTW)
-    if (n == 5 && CoutP == 64 && Cpad <= 80) {  // 16 positions = 25 row tiles, 4 channel tiles × 2 row groups of 13
-        if (B <= 256) TG_CONV_POS(2, 4, 1, 4);
-        if (B <= 512) TG_CONV_POS(4, 4, 2, 4);
-        if (B <= 1024) TG_CONV_POS(7, 4, 4, 4);
-        if (B <= 2048) TG_CONV_POS(13, 4, 8, 4);
-        TG_CONV_POS(13, 8, 16, 4);
-    }
-    if (n == 6 && CoutP % 128 == 0 && Cpad <= 128) {  // 4 positions = 9 row tiles, 8 channel tiles
-        if (B <= 256) TG_CONV_POS(3, 8, 1, 8);
-        if (B <= 512) TG_CONV_POS(5, 8, 2, 8);
-        TG_CONV_POS(9, 8, 4, 8);
-    }
-    if (n == 5 && CoutP % 128 == 0 && Cpad <= 128) {  // 8 positions = 200 rows in 13 row tiles, 8 channel tiles
-        if (B <= 256) TG_CONV_POS(2, 8, 1, 8);
-        if (B <= 512) TG_CONV_POS(4, 8, 2, 8);
-        if (B <= 1024) TG_CONV_POS(7, 8, 4, 8);
-        TG_CONV_POS(13, 8, 8, 8);
-    }
-#undef TG_CONV_POS
+    // whole-positions kernel where the shape divides evenly (the BASELINE configs; on 6×6 also layers of 256 output channels, two
+    // workgroup columns); generic tiles otherwise
+    const int pos_F = (n == 5 && CoutP == 64 && Cpad <= 80) ? 64 : ((n == 5 || n == 6) && CoutP % 128 == 0 && Cpad <= 128) ? 128 : 0;
+    if (pos_F)
+        return launch_pos_tiled(n, pos_F, B, [&](auto t) {
+            using Tl = decltype(t);
+            return launch_conv_pos_t<Tl::RTW, Tl::NWAVES>(st, in, Wp, bias, res, out, B, n, Cpad, CoutP, out_stride, cout_valid, relu, Tl::PW, Tl::CTW);
+        });
     if (conv_lds_bytes(2, n, Cpad) > 160 * 1024) {  // wide inputs (data gradient of the 6×6 policy head): 64-row tiles
         if (CoutP % 128 == 0) return launch_conv_t<1, 2>(st, in, Wp, bias, res, out, M, n, Cpad, CoutP, out_stride, cout_valid, relu);
         return launch_conv_t<1, 1>(st, in, Wp, bias, res, out, M, n, Cpad, CoutP, out_stride, cout_valid, relu);
@@ -2149,36 +2171,6 @@ bool tower_supported(int n, int F, int cin_pad) {
     return false;
 }
 
-hipError_t launch_tower(hipStream_t st, const float* in, const TowerParams& T, float* out, int B, int n) {
-    {
-        hipError_t herr;
-        if (launch_tower_halo<false>(st, in, T, out, B, n, &herr)) return herr;
-    }
-    // A workgroup's run time is that of its positions' row tiles, whatever the batch: with 16 positions per workgroup a
-    // 32-position call (the reference's BATCH_SIZE) ran 2 workgroups for as long as 4096 positions take.  Small batches
-    // therefore use instantiations with fewer positions (row tiles) per workgroup; the per-element arithmetic — taps,
-    // chunks, MFMA k-steps in the same order — does not depend on the tiling, so results are bit-identical.
-    if (n == 5 && T.F == 64 && T.cin_pad == 80) {
-        if (B <= 256) return launch_tower_t<2, 4, 5, 4, false>(st, in, T, out, B, n, 1, 4);
-        if (B <= 512) return launch_tower_t<4, 4, 5, 4, false>(st, in, T, out, B, n, 2, 4);
-        if (B <= 1024) return launch_tower_t<7, 4, 5, 4, false>(st, in, T, out, B, n, 4, 4);
-        if (B <= 2048) return launch_tower_t<13, 4, 5, 4, false>(st, in, T, out, B, n, 8, 4);
-        return launch_tower_t<13, 8, 5, 4, false>(st, in, T, out, B, n, 16, 4);
-    }
-    if (n == 6 && T.F == 128 && T.cin_pad == 96) {
-        if (B <= 256) return launch_tower_t<3, 8, 6, 8, false>(st, in, T, out, B, n, 1, 8);
-        if (B <= 512) return launch_tower_t<5, 8, 6, 8, false>(st, in, T, out, B, n, 2, 8);
-        return launch_tower_t<9, 8, 6, 8, false>(st, in, T, out, B, n, 4, 8);
-    }
-    if (n == 5 && T.F == 128 && T.cin_pad == 80) {
-        if (B <= 256) return launch_tower_t<2, 8, 5, 8, false>(st, in, T, out, B, n, 1, 8);
-        if (B <= 512) return launch_tower_t<4, 8, 5, 8, false>(st, in, T, out, B, n, 2, 8);
-        if (B <= 1024) return launch_tower_t<7, 8, 5, 8, false>(st, in, T, out, B, n, 4, 8);
-        return launch_tower_t<13, 8, 5, 8, false>(st, in, T, out, B, n, 8, 8);
-    }
-    return hipErrorInvalidValue;
-}
-
 // Does workgroup id i of a 1-D grid run on XCD i mod 8 on this device (every XCD its own L2)?  64 workgroups report HW_REG_XCC_ID.
 __global__ void k_xcc_probe(unsigned* __restrict__ out) {
     unsigned x;
@@ -2245,62 +2237,32 @@ static bool launch_tower_split(hipStream_t st, const uint8_t* states, const Towe
     return false;
 }
 
+// The fused tower: full batches on the halo / square-tile image, small batches of wide networks split by channel tile (states entry
+// with a scratch buffer), everything else on k_tower with the whole-position tilings.  FROM_STATES: `in` holds packed game states,
+// encoded in-kernel; with T.cb layer 0 runs over the board planes alone (identical bits for every batch size).
+template <bool FROM_STATES>
+static hipError_t launch_tower_impl(hipStream_t st, const float* in, const TowerParams& T, float* out, int B, int n, float* scratch) {
+    hipError_t herr;
+    if (launch_tower_halo<FROM_STATES>(st, in, T, out, B, n, &herr)) return herr;
+    if (FROM_STATES && launch_tower_split(st, (const uint8_t*)in, T, out, scratch, B, n, &herr)) return herr;
+    if (!(FROM_STATES && T.cb) && !tower_supported(n, T.F, T.cin_pad)) return hipErrorInvalidValue;
+    return launch_pos_tiled(n, T.F, B, [&](auto t) {
+        using Tl = decltype(t);
+        constexpr int CH = Tl::F / 16, CH0 = Tl::N == 5 ? 5 : 6;  // layer 0 over the 80 / 96 channels of the input planes
+        if constexpr (FROM_STATES)
+            if (T.cb) return launch_tower_t<Tl::RTW, Tl::NWAVES, 2, CH, true, true>(st, in, T, out, B, n, Tl::PW, Tl::CTW);
+        return launch_tower_t<Tl::RTW, Tl::NWAVES, CH0, CH, FROM_STATES>(st, in, T, out, B, n, Tl::PW, Tl::CTW);
+    });
+}
+
+hipError_t launch_tower(hipStream_t st, const float* in, const TowerParams& T, float* out, int B, int n) {
+    return launch_tower_impl<false>(st, in, T, out, B, n, nullptr);
+}
+
 // same, with the input planes encoded in-kernel from packed game states.  scratch (optional): a second activation buffer of the
 // batch's size — with it small batches of wide networks run split by channel tile (k_tower_split)
 hipError_t launch_tower_states(hipStream_t st, const uint8_t* states, const TowerParams& T, float* out, int B, int n, float* scratch) {
-    const float* in = (const float*)states;
-    {
-        hipError_t herr;
-        if (launch_tower_halo<true>(st, in, T, out, B, n, &herr)) return herr;
-        if (launch_tower_split(st, states, T, out, scratch, B, n, &herr)) return herr;
-    }
-    if (T.cb) {  // the same tilings with layer 0 over the board planes (identical bits for every batch size)
-        if (n == 5 && T.F == 64) {
-            // (round 6, measured at 300 … 2048 positions with 1 / 2 / 4 / 8 positions per workgroup: these brackets are within 11 % of the
-            // best choice everywhere — two co-resident workgroups of half the size take as long as one; eight waves instead of four: 5 %;
-            // every layer streaming the same L2-hot weights: no difference — profiles/r06_e_tower_pw_sweep.txt)
-            if (B <= 256) return launch_tower_t<2, 4, 2, 4, true, true>(st, in, T, out, B, n, 1, 4);
-            if (B <= 512) return launch_tower_t<4, 4, 2, 4, true, true>(st, in, T, out, B, n, 2, 4);
-            if (B <= 1024) return launch_tower_t<7, 4, 2, 4, true, true>(st, in, T, out, B, n, 4, 4);
-            if (B <= 2048) return launch_tower_t<13, 4, 2, 4, true, true>(st, in, T, out, B, n, 8, 4);
-            return launch_tower_t<13, 8, 2, 4, true, true>(st, in, T, out, B, n, 16, 4);
-        }
-        if (n == 6 && T.F == 128) {
-            if (B <= 256) return launch_tower_t<3, 8, 2, 8, true, true>(st, in, T, out, B, n, 1, 8);
-            if (B <= 512) return launch_tower_t<5, 8, 2, 8, true, true>(st, in, T, out, B, n, 2, 8);
-            return launch_tower_t<9, 8, 2, 8, true, true>(st, in, T, out, B, n, 4, 8);
-        }
-        if (n == 5 && T.F == 128) {
-            if (B <= 256) return launch_tower_t<2, 8, 2, 8, true, true>(st, in, T, out, B, n, 1, 8);
-            if (B <= 512) return launch_tower_t<4, 8, 2, 8, true, true>(st, in, T, out, B, n, 2, 8);
-            if (B <= 1024) return launch_tower_t<7, 8, 2, 8, true, true>(st, in, T, out, B, n, 4, 8);
-            return launch_tower_t<13, 8, 2, 8, true, true>(st, in, T, out, B, n, 8, 8);
-        }
-        return hipErrorInvalidValue;
-    }
-    if (n == 5 && T.F == 64 && T.cin_pad == 80) {
-        // fewer positions per workgroup for small batches (see tower_small_batch below): identical bits, shorter critical path
-        if (B <= 256) return launch_tower_t<2, 4, 5, 4, true>(st, in, T, out, B, n, 1, 4);
-        if (B <= 512) return launch_tower_t<4, 4, 5, 4, true>(st, in, T, out, B, n, 2, 4);
-        if (B <= 1024) return launch_tower_t<7, 4, 5, 4, true>(st, in, T, out, B, n, 4, 4);
-        if (B <= 2048) return launch_tower_t<13, 4, 5, 4, true>(st, in, T, out, B, n, 8, 4);
-        static const int variant = env_int("TG_TOWER_VARIANT");
-        if (variant == 16) return launch_tower_t<7, 16, 5, 4, true>(st, in, T, out, B, n, 16, 4);
-        if (variant == 4) return launch_tower_t<25, 4, 5, 4, true>(st, in, T, out, B, n, 16, 4);
-        return launch_tower_t<13, 8, 5, 4, true>(st, in, T, out, B, n, 16, 4);
-    }
-    if (n == 6 && T.F == 128 && T.cin_pad == 96) {
-        if (B <= 256) return launch_tower_t<3, 8, 6, 8, true>(st, in, T, out, B, n, 1, 8);
-        if (B <= 512) return launch_tower_t<5, 8, 6, 8, true>(st, in, T, out, B, n, 2, 8);
-        return launch_tower_t<9, 8, 6, 8, true>(st, in, T, out, B, n, 4, 8);
-    }
-    if (n == 5 && T.F == 128 && T.cin_pad == 80) {
-        if (B <= 256) return launch_tower_t<2, 8, 5, 8, true>(st, in, T, out, B, n, 1, 8);
-        if (B <= 512) return launch_tower_t<4, 8, 5, 8, true>(st, in, T, out, B, n, 2, 8);
-        if (B <= 1024) return launch_tower_t<7, 8, 5, 8, true>(st, in, T, out, B, n, 4, 8);
-        return launch_tower_t<13, 8, 5, 8, true>(st, in, T, out, B, n, 8, 8);
-    }
-    return hipErrorInvalidValue;
+    return launch_tower_impl<true>(st, (const float*)states, T, out, B, n, scratch);
 }
 
 // the FC kernels of the 5×5 policy head: K-steps of 64, the 99 tiles of softmax.cuh's geometry inside NP columns
@@ -2336,8 +2298,7 @@ hipError_t launch_gemm(hipStream_t st, const float* A, int lda, const float* Wp,
     }
     // Round 4: plain row-major GEMMs whose 25x output tiles split into 2x blocks of 12 + x leftover tiles take the ring too — the FC
     // head's data gradient in the training step (dlogits[4000 × 1600] · Wᵀ → 3200 columns = 200 tiles): 465 µs in k_gemm below
-    static const bool ring_gemm = !env_on("TG_NO_RING_GEMM");
-    if (ring_gemm && K % FC_KSTEP == 0 && NP % 400 == 0 && M > FC_SMALL_ROWS && !a_frag && !stats && !gather) {
+    if (K % FC_KSTEP == 0 && NP % 400 == 0 && M > FC_SMALL_ROWS && !a_frag && !stats && !gather) {
         static LdsAttr lds_attr;
         if (hipError_t e = lds_attr.ensure((const void*)k_fc_ring<1>, FC_RING_LDS); e != hipSuccess) return e;
         hipLaunchKernelGGL(k_fc_ring<1>, dim3((M + 127) / 128, NP / 200), dim3(512), FC_RING_LDS, st, A, lda, Wp, bias, out, M, K, NP, out_stride, n_valid, 0,

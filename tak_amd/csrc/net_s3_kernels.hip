@@ -19,7 +19,7 @@
 // The A operand (16 output channels × 32 k) is two 16-B loads of the pre-split weights [chunk][tile][hi|lo][q][cout]; a wave
 // owns 2 channel tiles × RTW row tiles (every activation fragment feeds 6 MFMAs) and its 32 output channels are ordered so
 // that lane group q ends up with channels 8q … 8q + 7 — one hi and one lo slot of the image (net.hip upload_conv_s3).
-//   k_fc_s3b / k_fc_s3, k_value_head_s3   policy FC and value head on the split activations.
+//   k_fc_s3b, k_fc_s3_ring, k_value_head_s3   policy FC (≤ 512 rows / full batches) and value head on the split activations.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -408,7 +408,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_tower_s3(const voi
         for (int j = 0; j < RTW; j++) { acc[j][0] = nxt[j][0]; acc[j][1] = nxt[j][1]; }
         __syncthreads();
         if (OUT_SPLIT && layer + 1 == T.nlayers) {
-            // the image now holds the final activations in the split row layout k_fc_s3 reads: copy it out, 16 B per lane
+            // the image now holds the final activations in the split row layout the split FC reads: copy it out, 16 B per lane
             const int spr = F >> 2;  // slots per row without the pad
             u32x4* o = (u32x4*)out + (size_t)pos0 * nsq * spr;
             for (int idx = tid; idx < rows * spr; idx += NW * 64) {
@@ -747,135 +747,12 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_tower_s3_halo(cons
 
 // ------------------------------------------------------------------------------------------------
 // Policy FC (net5.rs:56-61,108) on split operands: logits[M][N] = S[M][K]·W[K][N] + b with S in the split row
-// layout the tower writes.  Workgroup = 128 positions × 208 outputs (13 tiles), 8 waves = 4 position pairs × 2
-// output halves (7 + 6 tiles): a wave's weight fragment (LDS) feeds 2 position tiles × 3 MFMAs.  Weights are staged
-// global → LDS per K-step of 64, double buffered, in planes [chunk][q][hi|lo][208] of 16-byte slots (a quarter-wave
-// reads 16 consecutive slots: conflict free); the activations are the MFMA B operand straight from global.
-// ------------------------------------------------------------------------------------------------
-constexpr int FS_CT = 13;
-constexpr int FS_COLS = FS_CT * 16;               // 208
-constexpr int FS_SLOTS = 2 * 4 * 2 * FS_COLS;     // 3328 slots per K-step of 64
-
-__global__ __launch_bounds__(512) void k_fc_s3(const u32x4* __restrict__ A, const u32x4* __restrict__ Wp, const float* __restrict__ bias,
-                                               float* __restrict__ out, int M, int K, int NP, int out_stride, int n_valid) {
-    __shared__ u32x4 wl[2][FS_SLOTS];  // 106.5 KB
-    const int tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63;
-    const int r16 = lane & 15, q = lane >> 4;
-    const int pp = wave & 3, oh = wave >> 2;
-    const int t0 = oh * 7, NT = oh ? 6 : 7;
-    const int n0 = blockIdx.y * FS_COLS;
-    const int rpitch = K >> 2;  // slots per activation row
-    int row[2];
-    bool row_ok[2];
-    const u32x4* ap[2];
-#pragma unroll
-    for (int p = 0; p < 2; p++) {
-        row[p] = blockIdx.x * 128 + pp * 32 + p * 16 + r16;
-        row_ok[p] = row[p] < M;
-        ap[p] = A + (size_t)(row_ok[p] ? row[p] : M - 1) * rpitch + q;  // rows past the end load a valid row; never stored
-    }
-    const int nsteps = K / 64;
-    // staging: the global layout [chunk][column block][q][hi|lo][208] is the LDS plane layout, so both the global read
-    // and the LDS write of a K-step are linear in the thread index (coalesced, bank-conflict free)
-    const int ncb = NP / FS_COLS;
-    auto stage_load = [&](int step, u32x4 (&r)[7]) {
-#pragma unroll
-        for (int u = 0; u < 7; u++) {
-            // every load is unconditional (a clamped index for the idle tail of the last round): exec-masked loads
-            // make hipcc fall back to s_waitcnt vmcnt(0) right behind them
-            int idx = u * 512 + tid;
-            idx = idx < FS_SLOTS ? idx : FS_SLOTS - 1;
-            int c = idx / (FS_COLS * 8), rem = idx - c * (FS_COLS * 8);
-            r[u] = Wp[((size_t)(step * 2 + c) * ncb + blockIdx.y) * (FS_COLS * 8) + rem];
-        }
-    };
-    auto stage_store = [&](int buf, const u32x4 (&r)[7]) {
-#pragma unroll
-        for (int u = 0; u < 7; u++) {
-            int idx = u * 512 + tid;
-            if (idx < FS_SLOTS) wl[buf][idx] = r[u];
-        }
-    };
-    f32x4 acc[2][7];
-#pragma unroll
-    for (int p = 0; p < 2; p++)
-#pragma unroll
-        for (int j = 0; j < 7; j++) acc[p][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    u32x4 stg[7];
-    stage_load(0, stg);
-    stage_store(0, stg);
-    // the activation fragments of a whole K-step (2 chunks × 2 position tiles × hi/lo) are loaded one step ahead:
-    // 84 MFMAs (≥ 1300 cycles) cover an Infinity-Cache / HBM round trip
-    u32x4 ac[2][2][2], an[2][2][2];  // [chunk][position tile][hi, lo]
-    auto load_a = [&](int step, u32x4 (&a)[2][2][2]) {
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                a[c][p][0] = ap[p][(step * 2 + c) * 8];
-                a[c][p][1] = ap[p][(step * 2 + c) * 8 + 4];
-            }
-    };
-    load_a(0, ac);
-    __syncthreads();
-    for (int step = 0; step < nsteps; step++) {
-        const int buf = step & 1;
-        const int nx = step + 1 < nsteps ? step + 1 : step;  // the last step reloads itself (unused)
-        stage_load(nx, stg);
-        load_a(nx, an);
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const u32x4* wh = &wl[buf][((c * 4 + q) * 2 + 0) * FS_COLS + t0 * 16 + r16];
-            const u32x4* wo = &wl[buf][((c * 4 + q) * 2 + 1) * FS_COLS + t0 * 16 + r16];
-            // all weight fragments of the chunk are requested before the first MFMA (the tile-7 slot of the 6-tile waves
-            // reads a valid, unused address)
-            u32x4 w_h[7], w_l[7];
-#pragma unroll
-            for (int j = 0; j < 7; j++) {
-                const int jj = j < NT ? j : 0;
-                w_h[j] = wh[jj * 16];
-                w_l[j] = wo[jj * 16];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < 7; j++) {
-                if (j < NT) {
-#pragma unroll
-                    for (int p = 0; p < 2; p++) acc[p][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf(w_h[j]), as_bf(ac[c][p][0]), acc[p][j], 0, 0, 0);
-#pragma unroll
-                    for (int p = 0; p < 2; p++) acc[p][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf(w_h[j]), as_bf(ac[c][p][1]), acc[p][j], 0, 0, 0);
-#pragma unroll
-                    for (int p = 0; p < 2; p++) acc[p][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf(w_l[j]), as_bf(ac[c][p][0]), acc[p][j], 0, 0, 0);
-                }
-            }
-        }
-        stage_store(buf ^ 1, stg);  // (after the last step: into the buffer nobody reads any more)
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int p = 0; p < 2; p++) { ac[c][p][0] = an[c][p][0]; ac[c][p][1] = an[c][p][1]; }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int p = 0; p < 2; p++)
-        if (row_ok[p]) {
-#pragma unroll
-            for (int j = 0; j < 7; j++) {
-                const int nn = n0 + (t0 + j) * 16 + 4 * q;
-                if (j < NT && nn < n_valid) {
-                    f32x4 v = acc[p][j] + *(const f32x4*)&bias[nn];
-                    float* o = out + (size_t)row[p] * out_stride + nn;
-                    if (nn + 3 < n_valid) *(f32x4*)o = v;
-                    else for (int t = 0; t < 4; t++) if (nn + t < n_valid) o[t] = v[t];
-                }
-            }
-        }
-}
-
-// Variant with small workgroups: NW waves, each 2 position tiles × all CT output tiles (NW·32 positions × CT·16
-// outputs per workgroup).  CT = 7, NW = 4 needs 57 KB of LDS, so two workgroups share a CU and one's staging / barrier
-// phases overlap the other's MFMAs; nothing is loaded twice by a workgroup.
+// layout the tower writes.  NW waves, each 2 position tiles × all CT output tiles (NW·32 positions × CT·16 outputs per
+// workgroup): a wave's weight fragment (LDS) feeds 2 position tiles × 3 MFMAs.  Weights are staged global → LDS per
+// K-step of 64, double buffered, in planes [chunk][q][hi|lo][CT·16] of 16-byte slots (a quarter-wave reads 16 consecutive
+// slots: conflict free); the activations are the MFMA B operand straight from global.  CT = 7, NW = 4 needs 57 KB of LDS,
+// so two workgroups share a CU and one's staging / barrier phases overlap the other's MFMAs; nothing is loaded twice by a
+// workgroup.
 // stats (optional): the block-wise softmax statistics of softmax.cuh over this workgroup's CT·16 columns, per row:
 // stats[(row·blocks + block)·2] = {max, Σ exp(x − max)} of the columns < n_soft — what the tree backup and k_softmax_stats combine
 template <int CT, int NW>
@@ -1337,11 +1214,7 @@ static hipError_t launch_s3(hipStream_t st, const void* in, const TowerS3Params&
         if (n == 6 && T.F == 128) return launch_s3_halo_t<5, 3, 4, 6, FROM_STATES, OUT_SPLIT, 8>(st, in, T, out, B, 4, 4);
     }
     // 5×5, F = 64: 8 positions = 13 row tiles = 2 row groups (7,6) × 2 channel groups, 4 waves, two workgroups per CU
-    if (n == 5 && T.F == 64) {
-        static const bool wide = env_on("TG_S3_WIDE");  // A/B switch: one 8-wave workgroup of 16 positions per CU
-        if (wide) return launch_s3_t<7, 3, 2, FROM_STATES, OUT_SPLIT, 8>(st, in, T, out, B, n, 16, 2);
-        return launch_s3_t<7, 3, 2, FROM_STATES, OUT_SPLIT, 4>(st, in, T, out, B, n, 8, 2);
-    }
+    if (n == 5 && T.F == 64) return launch_s3_t<7, 3, 2, FROM_STATES, OUT_SPLIT, 4>(st, in, T, out, B, n, 8, 2);
     // 5×5, F = 128: 8 positions = 13 row tiles = 2 row groups (7,6) × 4 channel groups
     if (n == 5 && T.F == 128) return launch_s3_t<7, 3, 4, FROM_STATES, OUT_SPLIT, 8>(st, in, T, out, B, n, 8, 4);
     // 6×6, F = 128: 4 positions = 9 row tiles = 2 row groups (5,4) × 4 channel groups
@@ -1354,10 +1227,9 @@ hipError_t launch_tower_s3(hipStream_t st, const float* planes, const TowerS3Par
 hipError_t launch_tower_s3_states(hipStream_t st, const uint8_t* states, const TowerS3Params& T, float* out, int B, int n, bool out_split) {
     return out_split ? launch_s3<true, true>(st, states, T, out, B, n) : launch_s3<true, false>(st, states, T, out, B, n);
 }
-bool fc_s3_supported(int K, int NP) { return K % 64 == 0 && (NP % FS_COLS == 0 || NP % 112 == 0); }
-int fc_s3_cols(int NP) { return NP % 112 == 0 ? 112 : FS_COLS; }  // column-block width of the weight layout
+bool fc_s3_supported(int K, int NP) { return K % 64 == 0 && NP % FC_S3_COLS == 0; }
 bool fc_s3_ring_supported(int M, int K, int n_valid) { return K % 64 == 0 && n_valid <= FC_TILES * 16 && M > 512; }
-// Wp: the [chunk][column block][q][hi|lo][column] layout of k_fc_s3b / k_fc_s3 (≤ 512 rows); Wr (optional): the ring layout of
+// Wp: the [chunk][column block][q][hi|lo][column] layout of k_fc_s3b (≤ 512 rows); Wr (optional): the ring layout of
 // k_fc_s3_ring (full batches).  stats: the block statistics of softmax.cuh's geometry (the exact-f32 FC's), from the ring's epilogue
 // or by k_fc_stats behind k_fc_s3b — the same bits.  gather: as launch_gemm's (needs Wr and > 512 rows).
 hipError_t launch_fc_s3(hipStream_t st, const float* act_split, const void* Wp, const void* Wr, const float* bias, float* out, int M, int K, int NP,
@@ -1373,15 +1245,10 @@ hipError_t launch_fc_s3(hipStream_t st, const float* act_split, const void* Wp, 
                            gather ? nullptr : out, M, K, out_stride, n_valid, stats, n_soft, g);
         return hipGetLastError();
     }
-    if (gather) return hipErrorInvalidValue;
-    if (NP % 112 == 0) {
-        dim3 grid((M + 127) / 128, NP / 112);
-        hipLaunchKernelGGL((k_fc_s3b<7, 4>), grid, dim3(256), 0, st, (const u32x4*)act_split, (const u32x4*)Wp, bias, out, M, K, NP, out_stride, n_valid,
-                           nullptr, n_soft);
-    } else {
-        dim3 grid((M + 127) / 128, NP / FS_COLS);
-        hipLaunchKernelGGL(k_fc_s3, grid, dim3(512), 0, st, (const u32x4*)act_split, (const u32x4*)Wp, bias, out, M, K, NP, out_stride, n_valid);
-    }
+    if (gather || NP % FC_S3_COLS) return hipErrorInvalidValue;
+    dim3 grid((M + 127) / 128, NP / FC_S3_COLS);
+    hipLaunchKernelGGL((k_fc_s3b<FC_S3_COLS / 16, 4>), grid, dim3(256), 0, st, (const u32x4*)act_split, (const u32x4*)Wp, bias, out, M, K, NP, out_stride, n_valid,
+                       nullptr, n_soft);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     return stats ? launch_fc_stats(st, out, out_stride, M, n_soft, stats) : hipSuccess;
 }

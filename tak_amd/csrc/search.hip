@@ -253,8 +253,7 @@ static void bind_logits(TgEngine* e) {
     s->d.fc_stride = 0;
     s->d.child_logit = nullptr;
     net_set_gather(e, nullptr);
-    static const bool off = env_on("TG_DUAL_STREAM") || env_on("TG_NO_FUSED_SOFTMAX");
-    if (off || e->cfg.evaluator != TG_EVAL_RESNET) return;
+    if (e->cfg.evaluator != TG_EVAL_RESNET) return;
     int ld = 0;
     const float* lg = net_fc_logits(e, &ld);
     if (lg) {
@@ -302,103 +301,33 @@ static int search_iterate(TgEngine* e, const uint8_t* d_active) {
     return TG_OK;
 }
 
-// Rollouts on two streams (opt-in, TG_DUAL_STREAM=1): the games are split into two halves that run the select → network → backup chain
-// independently (they share nothing but read-only weights), so the latency-bound tree kernels of one half overlap the
-// MFMA kernels of the other.  Per-game results do not depend on the batch a position is evaluated in, so trees are
-// identical to the single-stream schedule.  An iteration the profiler samples runs alone on the engine stream.
-static SearchDev half_view(const SearchDev& d, int g0, int count, size_t state_bytes) {
-    SearchDev v = d;  // the node pool is shared: only the per-game arrays are offset
-    v.root += g0; v.alloc += 2 * (size_t)g0; v.chunk_head += g0;
-    v.root_state += (size_t)g0 * state_bytes; v.alive += g0; v.generation += g0;
-    v.path_len += g0; v.path += (size_t)g0 * MAX_DEPTH; v.leaf_kind += g0; v.leaf_hash += g0;
-    v.leaf_rec += 2 * (size_t)g0; v.child_pidx += (size_t)g0 * EX_MOVES; v.abort += g0;  // (dual stream runs with batch 1)
-    v.leaf_state += (size_t)g0 * state_bytes; v.policy += (size_t)g0 * d.P; v.eval += g0;
-    v.counters += (size_t)g0 * 2;
-    v.slot_base += (uint32_t)g0;
-    v.G = count;
-    return v;
-}
-
-static bool dual_stream_ok(TgEngine* e) {
-    // measured on MI355X at C2: no gain (exact f32 4.06 M vs 4.11 M expansions/s single-stream, bf16x3 11.8 M vs 12.4 M) —
-    // the half-batch MFMA kernels fill the chip less well than they overlap; kept opt-in
-    static const bool on = env_on("TG_DUAL_STREAM");
-    Search* s = e->search;
-    return on && s->d.batch == 1 && e->cfg.evaluator == TG_EVAL_RESNET && !s->d.planes && net_takes_states(e) && s->d.G >= 512;
-}
-
 static int search_iterate_many(TgEngine* e, int iters) {
     Search* s = e->search;
     if (iters <= 0) return TG_OK;
     bind_logits(e);
     GatherScope scope{e};
-    if (!dual_stream_ok(e)) {
-        if (s->d.batch == 1 && iters > 1 && !env_on("TG_NO_FUSED_BACKUP_SELECT")) {
-            // select(0) | net | backup(0)+select(1) | net | … | backup(iters-1): one tree kernel per iteration
-            SearchDev d = s->d;
-            d.pass = 0;
-            launch_select(e->stream, d, nullptr);
-            for (int i = 0; i < iters; i++) {
-                if (e->cfg.evaluator == TG_EVAL_RESNET) {
-                    float* pol = s->d.logits ? nullptr : s->d.policy;
-                    int rc = s->d.planes ? net_forward_dev(e, s->d.G, s->d.planes, pol, s->d.eval)
-                                         : net_forward_states_dev(e, s->d.G, s->d.leaf_state, pol, s->d.eval);
-                    if (rc) return rc;
-                }
-                if (i + 1 < iters) launch_backup_select(e->stream, d);
-                else launch_backup(e->stream, d);
-            }
-            TG_HIP(hipGetLastError());
-            return TG_OK;
-        }
+    if (s->d.batch == 1 && iters > 1) {
+        // select(0) | net | backup(0)+select(1) | net | … | backup(iters-1): one tree kernel per iteration
+        SearchDev d = s->d;
+        d.pass = 0;
+        launch_select(e->stream, d, nullptr);
         for (int i = 0; i < iters; i++) {
-            int rc = search_iterate(e, nullptr);
-            if (rc) return rc;
-        }
-        return TG_OK;
-    }
-    for (int h = 0; h < 2; h++)
-        if (!e->half_stream[h]) TG_HIP(hipStreamCreateWithFlags(&e->half_stream[h], hipStreamNonBlocking));
-    for (int k = 0; k < 3; k++)
-        if (!e->half_event[k]) TG_HIP(hipEventCreateWithFlags(&e->half_event[k], hipEventDisableTiming));
-    const int G = s->d.G;
-    const int g0 = (G / 2 + 15) / 16 * 16;  // whole workgroups of the tower in both halves
-    const SearchDev view[2] = {half_view(s->d, 0, g0, e->g.bytes), half_view(s->d, g0, G - g0, e->g.bytes)};
-    const int first[2] = {0, g0};
-    bool forked = false;
-    auto fork = [&]() -> int {
-        TG_HIP(hipEventRecord(e->half_event[2], e->stream));
-        for (int h = 0; h < 2; h++) TG_HIP(hipStreamWaitEvent(e->half_stream[h], e->half_event[2], 0));
-        forked = true;
-        return TG_OK;
-    };
-    auto join = [&]() -> int {
-        for (int h = 0; h < 2; h++) {
-            TG_HIP(hipEventRecord(e->half_event[h], e->half_stream[h]));
-            TG_HIP(hipStreamWaitEvent(e->stream, e->half_event[h], 0));
-        }
-        forked = false;
-        return TG_OK;
-    };
-    for (int i = 0; i < iters; i++) {
-        if (net_profile_due(e)) {  // timed alone, whole batch, on the engine stream
-            if (forked) { int rc = join(); if (rc) return rc; }
-            int rc = search_iterate(e, nullptr);
-            if (rc) return rc;
-            continue;
-        }
-        if (!forked) { int rc = fork(); if (rc) return rc; }
-        net_profile_skip(e);
-        for (int h = 0; h < 2; h++) {
-            hipStream_t st = e->half_stream[h];
-            launch_select(st, view[h], nullptr);
-            int rc = net_forward_states_at(e, view[h].G, view[h].leaf_state, view[h].policy, view[h].eval, st, first[h]);
-            if (rc) return rc;
-            launch_backup(st, view[h]);
+            if (e->cfg.evaluator == TG_EVAL_RESNET) {
+                float* pol = s->d.logits ? nullptr : s->d.policy;
+                int rc = s->d.planes ? net_forward_dev(e, s->d.G, s->d.planes, pol, s->d.eval)
+                                     : net_forward_states_dev(e, s->d.G, s->d.leaf_state, pol, s->d.eval);
+                if (rc) return rc;
+            }
+            if (i + 1 < iters) launch_backup_select(e->stream, d);
+            else launch_backup(e->stream, d);
         }
         TG_HIP(hipGetLastError());
+        return TG_OK;
     }
-    if (forked) return join();
+    for (int i = 0; i < iters; i++) {
+        int rc = search_iterate(e, nullptr);
+        if (rc) return rc;
+    }
     return TG_OK;
 }
 

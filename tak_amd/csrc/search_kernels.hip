@@ -1095,13 +1095,12 @@ __global__ void k_sp_count_ply(SelfPlayDev P) { P.stats[ST_PLIES] += 1; }
 // ---- launchers --------------------------------------------------------------------------------
 static inline dim3 wgrid(int G) { return dim3((G + WPB - 1) / WPB); }
 
-// the tree kernels are compiled for the board sizes of the BASELINE configs (n as a constant) and once for any size
-static const bool g_runtime_n = env_on("TG_RUNTIME_N");  // A/B: the generic instantiation for every size (same results)
+// the tree kernels are compiled for the board sizes of the BASELINE configs (n as a constant) and once for any size (3×3, 4×4)
 #define TG_BY_BOARD(KERNEL, ...)                                                                          \
     do {                                                                                                  \
-        if (S.n == 5 && !g_runtime_n) hipLaunchKernelGGL(KERNEL<5>, wgrid(S.G), dim3(WPB * 64), 0, st, __VA_ARGS__);      \
-        else if (S.n == 6 && !g_runtime_n) hipLaunchKernelGGL(KERNEL<6>, wgrid(S.G), dim3(WPB * 64), 0, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERNEL<0>, wgrid(S.G), dim3(WPB * 64), 0, st, __VA_ARGS__);                    \
+        if (S.n == 5) hipLaunchKernelGGL(KERNEL<5>, wgrid(S.G), dim3(WPB * 64), 0, st, __VA_ARGS__);      \
+        else if (S.n == 6) hipLaunchKernelGGL(KERNEL<6>, wgrid(S.G), dim3(WPB * 64), 0, st, __VA_ARGS__); \
+        else hipLaunchKernelGGL(KERNEL<0>, wgrid(S.G), dim3(WPB * 64), 0, st, __VA_ARGS__);               \
     } while (0)
 void launch_select(hipStream_t st, const SearchDev& S, const uint8_t* active) { TG_BY_BOARD(k_select, S, active); }
 void launch_backup(hipStream_t st, const SearchDev& S) { TG_BY_BOARD(k_backup, S); }
