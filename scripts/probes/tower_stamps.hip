@@ -35,7 +35,8 @@ int main(int argc, char** argv) {
     uint32_t* dmap; hipMalloc(&dmap, map.size() * 4); hipMemcpy(dmap, map.data(), map.size() * 4, hipMemcpyHostToDevice);
     T.slotmap = dmap; T.halo_pw = c5 ? 8 : 16; T.halo_ps = c5 ? 37 : 36;
     // variant 82: the halo tower with the constant input planes as a per-position bias (TowerParams.cb): layer 0 over 32 channels
-    if (variant == 82 || c5) {
+    // variant 83: the square-tile tower k_tower_sq<2, true, true> with the same parameters
+    if (variant == 82 || variant == 83 || c5) {
         size_t wf = (size_t)9 * 32 * F;
         float* w; hipMalloc(&w, wf * 4);
         std::vector<float> hw(wf);
@@ -46,6 +47,7 @@ int main(int argc, char** argv) {
     }
     auto launch = [&]() {
         if (c5) return launch_tower_halo_t<13, 8, 2, 8, 5, true, true>(nullptr, (const float*)states, T, out, B, 8);
+        if (variant == 83) return launch_tower_sq_t<2, true, true>(nullptr, (const float*)states, T, out, B);
         if (variant == 82) return launch_tower_halo_t<13, 8, 2, 4, 5, true, true>(nullptr, (const float*)states, T, out, B, 4);
         if (variant == 80) return launch_tower_halo_t<13, 8, 5, 4, 5, true>(nullptr, (const float*)states, T, out, B, 4);
         if (variant == 16) return launch_tower_t<7, 16, 5, 4, true>(nullptr, (const float*)states, T, out, B, n, 16, 4);
@@ -85,6 +87,23 @@ int main(int argc, char** argv) {
             acc[5] += (double)(nx[0] - s[0]);
             cnt++;
         }
+    if (variant == 83) {  // every layer, mean over the waves; `next` = barrier 2 released -> the next layer's loop entered
+        printf("layer | mainloop epilogue barrier1 writeback barrier2 next | layer (mean over 8 waves, s_memtime ticks)\n");
+        for (int l = 0; l < nl - 1; l++) {
+            double m[7] = {0, 0, 0, 0, 0, 0, 0};
+            for (int w = 0; w < nw; w++) {
+                const unsigned long long* s = &h[((size_t)l * 16 + w) * 8];
+                const unsigned long long* nx = &h[((size_t)(l + 1) * 16 + w) * 8];
+                for (int k = 0; k < 5; k++) m[k] += (double)(s[k + 1] - s[k]) / nw;
+                m[5] += (double)(nx[0] - s[5]) / nw;
+                m[6] += (double)(nx[0] - s[0]) / nw;
+            }
+            printf("%5d | %8.0f %8.0f %8.0f %9.0f %8.0f %4.0f | %.0f\n", l, m[0], m[1], m[2], m[3], m[4], m[5], m[6]);
+        }
+        const unsigned long long* f = &h[((size_t)(nl - 1) * 16) * 8];
+        const unsigned long long* z = &h[0];
+        printf("wave 0: kernel start -> last layer's loop left: %llu ticks (last layer's loop %llu)\n", f[1] - z[6], f[1] - f[0]);
+    }
     printf("mean over layers 1..%d, all waves: mainloop %.0f  epilogue %.0f  barrier1 %.0f  writeback %.0f  barrier2 %.0f | layer %.0f cycles (s_memtime ticks)\n",
            nl - 2, acc[0] / cnt, acc[1] / cnt, acc[2] / cnt, acc[3] / cnt, acc[4] / cnt, acc[5] / cnt);
     return 0;

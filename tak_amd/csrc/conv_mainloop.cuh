@@ -329,23 +329,25 @@ template <int N, typename Fn>
 __device__ __forceinline__ void static_for(Fn&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 // img4 = this lane's base: lds4 + position·sq_image_pitch4 + q.  acc[j] = tile sq_tile(RG, j).
-template <int RG, int CH>
+// CHL = 16-channel chunks per tap of THIS layer's input (CH for the F → F layers; layer 0 over the board planes: 2, in the first
+// 2·4 slots of the same cells), LAST_T = MFMAs of a tap's last chunk that hold real channels (conv_last_chunk_perm; 4: all).
+template <int RG, int CH, int CHL = CH, int LAST_T = 4>
 __device__ __forceinline__ void conv_mainloop_sq(const f32x4* __restrict__ img4, const float* __restrict__ wlayer,
                                                  const float* __restrict__ wnext, uint32_t wlane, f32x4 (&acc)[13], const int turn,
                                                  f32x4& w0, f32x4& w1) {
-    constexpr int STEPS = 9 * CH, ROW = 3 * CH, CP4 = sq_image_cell4<CH>();
+    constexpr int STEPS = 9 * CHL, ROW = 3 * CHL, CP4 = sq_image_cell4<CH>();
     constexpr size_t WCHUNK = (size_t)16 * CH * 4 * 16;
     static_assert(sq_tiles(RG) <= 13, "acc holds 13 tiles");
 #ifndef TG_PRIO_PERIOD
 #define TG_PRIO_PERIOD 2
 #endif
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wlayer, 0, (int)(9 * CH * WCHUNK), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wlayer, 0, (int)(STEPS * WCHUNK), 0x00020000);
     const __amdgpu_buffer_rsrc_t nrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wnext, 0, (int)(9 * CH * WCHUNK), 0x00020000);
     // step s = tap·CH + chunk: its on-board tiles, the first ⌈cnt/2⌉ of them in half 1; the 16-byte image offset of the k-th
-    constexpr auto cnt = [](int s) { return sq_tap_count(RG, s / CH); };
-    constexpr auto h1 = [](int s) { return (sq_tap_count(RG, s / CH) + 1) / 2; };
+    constexpr auto cnt = [](int s) { return sq_tap_count(RG, s / CHL); };
+    constexpr auto h1 = [](int s) { return (sq_tap_count(RG, s / CHL) + 1) / 2; };
     constexpr auto off = [](int s, int k) {
-        return (sq_tile(RG, sq_tap_tile(RG, s / CH, k)) + (s / CH / 3 - 1) * SQ_NB + (s / CH % 3 - 1)) * CP4 + (s % CH) * 4;
+        return (sq_tile(RG, sq_tap_tile(RG, s / CHL, k)) + (s / CHL / 3 - 1) * SQ_NB + (s / CHL % 3 - 1)) * CP4 + (s % CHL) * 4;
     };
     f32x4 a1[7], a2[7];  // the two halves' fragments of a step (≤ 13 tiles on the board)
     static_for<7>([&](auto K) {
@@ -368,8 +370,8 @@ __device__ __forceinline__ void conv_mainloop_sq(const f32x4* __restrict__ img4,
         static_for<4>([&](auto T) {
             static_for<7>([&](auto K) {
                 constexpr int t = decltype(T)::value, k = decltype(K)::value;
-                if constexpr (k < h1(s)) {
-                    constexpr int j = sq_tap_tile(RG, s / CH, k);
+                if constexpr (k < h1(s) && (s % CHL + 1 < CHL || t < LAST_T)) {
+                    constexpr int j = sq_tap_tile(RG, s / CHL, k);
                     acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[t], a1[k][t], acc[j], 0, 0, 0);
                 }
             });
@@ -389,8 +391,8 @@ __device__ __forceinline__ void conv_mainloop_sq(const f32x4* __restrict__ img4,
         static_for<4>([&](auto T) {
             static_for<7>([&](auto K) {
                 constexpr int t = decltype(T)::value, k = decltype(K)::value;
-                if constexpr (h1(s) + k < cnt(s)) {
-                    constexpr int j = sq_tap_tile(RG, s / CH, h1(s) + k);
+                if constexpr (h1(s) + k < cnt(s) && (s % CHL + 1 < CHL || t < LAST_T)) {
+                    constexpr int j = sq_tap_tile(RG, s / CHL, h1(s) + k);
                     acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[t], a2[k][t], acc[j], 0, 0, 0);
                 }
             });
@@ -405,6 +407,7 @@ __device__ __forceinline__ void conv_mainloop_sq(const f32x4* __restrict__ img4,
 }
 
 // chunks 0 and 1 of a layer's weights for the first conv_mainloop_halo call of a kernel
+// (CH = chunks per tap of the layer's input: the extent of the descriptor)
 template <int CH, int COT = CH>
 __device__ __forceinline__ void conv_halo_first_weights(const float* __restrict__ wlayer, uint32_t wlane, f32x4& w0, f32x4& w1) {
     constexpr size_t WCHUNK = (size_t)16 * COT * 4 * 16;

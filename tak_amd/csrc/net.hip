@@ -611,11 +611,13 @@ static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const ui
         // algorithmic FLOPs of one timed launch: one F→F conv (per-layer path) or the whole tower (fused)
         n->conv_flops = (n->fused || n->s3) ? 2ll * M * 9 * ((long long)n->cin * F + 2ll * n->R * F * F) : 2ll * M * 9 * F * F;
         // executed: with the constant planes as a bias layer 0 multiplies 16 + 4·cb_last_t input channels per tap, not cin; the
-        // square-tile tower issues the F → F layers' MFMAs of on-board (square, tap) pairs only (169 of 225 on 5×5)
+        // square-tile tower issues the MFMAs of on-board (square, tap) pairs only (169 of 225 on 5×5): in the F → F layers, and in
+        // layer 0 where it runs over the board planes
         if (n->fused && !n->s3) {
-            const long long c0 = (d_states && n->tower.cb) ? 16 + 4 * n->tower.cb_last_t : n->cin;
+            const bool cb0 = d_states && n->tower.cb;
+            const long long c0 = cb0 ? 16 + 4 * n->tower.cb_last_t : n->cin;
             const long long taps = tower_square_tiles(N, F, nb) ? (long long)nb * 169 : 9ll * M;  // (row, tap) pairs of a layer ≥ 1
-            n->conv_flops_exec = 2ll * M * 9 * c0 * F + 2ll * taps * 2ll * n->R * F * F;
+            n->conv_flops_exec = 2ll * (cb0 ? taps : 9ll * M) * c0 * F + 2ll * taps * 2ll * n->R * F * F;
         } else n->conv_flops_exec = n->conv_flops;
         chain->push_back(prof_event(n, st));
     }

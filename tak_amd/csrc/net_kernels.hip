@@ -16,8 +16,8 @@
 //                           off-board taps, per-tap masks): batches below 2048 / 1024 / 512 positions
 //   k_tower_halo            the same tower on the HALO image (zero cells between board rows and positions, taps as
 //                           ds_read immediates, conflict-free slot table): full batches, 89 – 94 % of the MFMA peak
-//   k_tower_sq              5×5 with 64 filters at full batches: layers ≥ 1 on square tiles (tile = board square, column =
-//                           position), only the MFMAs of on-board taps issued (169 of 225); same bits
+//   k_tower_sq              5×5 with 64 filters at full batches: square tiles (tile = board square, column = position), only
+//                           the MFMAs of on-board taps issued (169 of 225), layer 0 over the board planes included; same bits
 //   k_gemm                  generic GEMM
 //   k_fc_ring               policy FC for full batches: LDS-DMA ring of three K-steps, flag counters instead of barriers
 //   k_fc_small              policy FC for ≤ 2048 rows (no LDS, no barrier)
@@ -348,6 +348,43 @@ __device__ __forceinline__ void tower_stage_states_cb(f32x4* lds4, f32x4* pb4, c
         const WRaw r1 = ws_load_raw(states + (size_t)(pos0 + (p1 < npos ? p1 : p)) * geo.bytes, geo);
         stage_one(p, r0);
         if (p1 < npos) stage_one(p1, r1);
+    }
+}
+// The same for k_tower_sq, straight into the square-tile image (conv_mainloop_sq): the 32 board-plane channels of square sq of
+// position p in the first 8 slots of cell (p, sq); PB behind the image.  The positions a ragged workgroup lacks get zero planes
+// (their columns are computed and never stored; what they read must be finite).
+template <int NWAVES, int CH>
+__device__ __forceinline__ void tower_stage_states_cb_sq(f32x4* lds4, f32x4* pb4, const uint8_t* states, int pos0, int npos,
+                                                         const TowerParams& T) {
+    constexpr int n = SQ_NB, nsq = n * n, PW = 16, PP4 = sq_image_pitch4<CH>(), CP4 = sq_image_cell4<CH>(), LAST_T = 3;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const Geom geo = make_geom(n);
+    auto stage_one = [&](int p, const WRaw& raw) {
+        WState ws;
+        ws_unpack(ws, raw, geo);
+        const float fcd = fcd_value(ws, geo);
+        const RowMask m = ws_row_mask(ws, geo);
+        if (lane < nsq) {
+            f32x4* cell = lds4 + p * PP4 + lane * CP4;
+            f32x4 qd[8];
+            tower_cb_board_quads(m, n, qd);
+#pragma unroll
+            for (int k = 0; k < 4; k++) cell[k] = qd[k];
+            const f32x4 lc[4] = {qd[4], qd[5], qd[6], qd[7]};
+            conv_last_chunk_store(cell + 4, lc, LAST_T);
+        }
+        tower_cb_table(ws, fcd, n, p, 4 * CH, (const f32x4*)T.cplane_sums, (const f32x4*)T.b[0], pb4);
+    };
+    for (int p = wave; p < npos; p += 2 * NWAVES) {
+        const int p1 = p + NWAVES;
+        const WRaw r0 = ws_load_raw(states + (size_t)(pos0 + p) * geo.bytes, geo);
+        const WRaw r1 = ws_load_raw(states + (size_t)(pos0 + (p1 < npos ? p1 : p)) * geo.bytes, geo);
+        stage_one(p, r0);
+        if (p1 < npos) stage_one(p1, r1);
+    }
+    for (int idx = threadIdx.x; idx < (PW - npos) * nsq * 8; idx += NWAVES * 64) {
+        const int c = idx >> 3;
+        lds4[(npos + c / nsq) * PP4 + (c % nsq) * CP4 + (idx & 7)] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
 }
 
@@ -937,9 +974,13 @@ __global__ __launch_bounds__(NWAVES * 64) void k_tower_halo(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
-// The fused tower of 5×5 boards with 64 filters at full batches (16 positions per workgroup): staging and layer 0 as in
-// k_tower_halo, layers 1 … on the square-tile image of conv_mainloop_sq — row tile = board square, tile column = position
-// of the workgroup — whose main loop issues the MFMAs of the on-board taps only: 169 of the 225 (square, tap) pairs.
+// The fused tower of 5×5 boards with 64 filters at full batches (16 positions per workgroup) on the square-tile image of
+// conv_mainloop_sq — row tile = board square, tile column = position of the workgroup — whose main loop issues the MFMAs
+// of the on-board taps only: 169 of the 225 (square, tap) pairs.
+// Layer 0 with the constant planes as a bias (CB, the states entry) runs on the same image: the board planes are staged into the
+// first 8 slots of every cell (tower_stage_states_cb_sq), the loop runs 2 chunks per tap and the 3 real MFMAs of the last
+// one, a tile's border class — which row of PB its epilogue adds — is a constant, and its outputs take the write-back of
+// every other layer.  Without CB (planes entry, 80 input channels) layer 0 stays on the plain image as in k_tower_halo.
 // Waves w = 4·rg + ct: channel tile ct, row group rg (its squares: sq_tile); waves w and w + 4 share a SIMD.
 // Per-element arithmetic in k_tower's order, minus additions of exact zeros → identical bits.
 // ------------------------------------------------------------------------------------------------
@@ -967,6 +1008,21 @@ __device__ __forceinline__ void tower_sq_writeback(f32x4* cell4, f32x4 (&acc)[13
     }
 }
 
+// layer 0's epilogue on square tiles: + PB[position][border class of the tile's square][channels], ReLU (pbq = PB + this lane's
+// position and channel quad)
+template <int RG, int CH>
+__device__ __forceinline__ void tower_sq_cb_epilogue(const f32x4* pbq, f32x4 (&acc)[13]) {
+#pragma unroll
+    for (int j = 0; j < sq_tiles(RG); j++) {
+        constexpr int n = SQ_NB;
+        const int sq = sq_tile(RG, j), y = sq / n, x = sq % n;
+        const int cls = (y == 0 ? 0 : y == n - 1 ? 2 : 1) * 3 + (x == 0 ? 0 : x == n - 1 ? 2 : 1);  // tower_cb_index
+        f32x4 v = acc[j] + pbq[cls * 4 * CH];
+        v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
+        acc[j] = v;
+    }
+}
+
 template <int CH0, bool FROM_STATES, bool CB = false>
 __global__ __launch_bounds__(512) void k_tower_sq(const float* __restrict__ in, TowerParams T, float* __restrict__ out, int B) {
     static_assert(!CB || FROM_STATES, "the constant-plane bias needs the packed states");
@@ -985,41 +1041,80 @@ __global__ __launch_bounds__(512) void k_tower_sq(const float* __restrict__ in, 
     const uint32_t wlane = (uint32_t)(((ch0 + r16) * 4 + q) * 16);  // this lane's 16 B inside a chunk of weights
     f32x4 w0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, w1 = w0;                // the weight stream's two chunks in flight between layers
     f32x4 acc[RTW];
-    int rho0, my_tiles;
-    tower_plain_layer0<RTW, NWAVES, CH0, CH, NB, FROM_STATES, CB>(in, T, lds4, PW, pos0, npos, CTW, wlane, acc, rho0, my_tiles, w0, w1);
-    if (T.nlayers == 1) {  // no residual block: layer 0 is the tower's output
+    int ad = r16 * PP4 + q;  // this lane's tile column is position r16
+    const int turn = rg;     // waves w and w + 4 share a SIMD
+    if constexpr (CB) {
+        // ---- layer 0 on square tiles ----
+        static_assert(CH0 == 2, "board planes: 32 channels");
+        f32x4* pb4 = lds4 + PW * PP4;  // PB[position][class][F] behind the image
+        tower_stage_states_cb_sq<NWAVES, CH>(lds4, pb4, (const uint8_t*)in, pos0, npos, T);
+        conv_halo_first_weights<CH0, CH>(T.w0_board, wlane, w0, w1);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < RTW; j++) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        asm volatile("" : "+v"(ad));
+        TG_STAMP(0, 0);
+        const float* wnext = T.nlayers > 1 ? T.w[1] : T.w0_board;
+        if (rg == 0) conv_mainloop_sq<0, CH, CH0, 3>(lds4 + ad, T.w0_board, wnext, wlane, acc, turn, w0, w1);
+        else conv_mainloop_sq<1, CH, CH0, 3>(lds4 + ad, T.w0_board, wnext, wlane, acc, turn, w0, w1);
+        TG_STAMP(0, 1);
+        // (a missing position of a ragged workgroup has no row of PB: position 0's, finite, never stored)
+        const f32x4* pbq = pb4 + (r16 < npos ? r16 : 0) * 9 * 4 * CH + (ch0 >> 2) + q;
+        if (rg == 0) tower_sq_cb_epilogue<0, CH>(pbq, acc);
+        else tower_sq_cb_epilogue<1, CH>(pbq, acc);
+        if (T.nlayers == 1) {  // no residual block: layer 0 is the tower's output
+            if (r16 < npos) {
+                int p = pos0 + r16;
+                asm volatile("" : "+v"(p));
+                if (rg == 0) tower_sq_store<0, CH>(acc, T, out, p, q, ct);
+                else tower_sq_store<1, CH>(acc, T, out, p, q, ct);
+            }
+            return;
+        }
+        TG_STAMP(0, 2);
+        __syncthreads();  // every wave has finished reading the board planes and PB
+        TG_STAMP(0, 3);
+        f32x4* cell4 = lds4 + ad + (ch0 >> 2);
+        if (rg == 0) tower_sq_writeback<0, CH>(cell4, acc, false);
+        else tower_sq_writeback<1, CH>(cell4, acc, false);
+        TG_STAMP(0, 4);
+        __syncthreads();
+        TG_STAMP(0, 5);
+    } else {  // layer 0 on the plain image (tile = 16 consecutive rows), then the change of images
+        int rho0, my_tiles;
+        tower_plain_layer0<RTW, NWAVES, CH0, CH, NB, FROM_STATES, CB>(in, T, lds4, PW, pos0, npos, CTW, wlane, acc, rho0, my_tiles, w0, w1);
+        if (T.nlayers == 1) {  // no residual block: layer 0 is the tower's output
+#pragma unroll
+            for (int j = 0; j < RTW; j++) {
+                const int rho = rho0 + j * 16;
+                if (j < my_tiles && rho < npos * nsq) {
+                    const int p = pos0 + rho / nsq, sq = rho % nsq;
+                    if (T.frag_out) ((f32x4*)out)[((size_t)(p >> 4) * (nsq * CH) + sq * CH + ct) * 64 + (p & 15) * 4 + q] = acc[j];
+                    else *(f32x4*)&out[((size_t)pos0 * nsq + rho) * (16 * CH) + ch0 + 4 * q] = acc[j];
+                }
+            }
+            return;
+        }
+        TG_STAMP(0, 2);
+        __syncthreads();  // every wave has finished reading the input planes
+        TG_STAMP(0, 3);
+        // the square-tile image replaces them.  Every cell of all PW positions is written: the rows of a ragged workgroup's missing
+        // positions read the zero row in layer 0, so their cells hold finite values (bias, ReLU) that later layers read and never store
 #pragma unroll
         for (int j = 0; j < RTW; j++) {
             const int rho = rho0 + j * 16;
-            if (j < my_tiles && rho < npos * nsq) {
-                const int p = pos0 + rho / nsq, sq = rho % nsq;
-                if (T.frag_out) ((f32x4*)out)[((size_t)(p >> 4) * (nsq * CH) + sq * CH + ct) * 64 + (p & 15) * 4 + q] = acc[j];
-                else *(f32x4*)&out[((size_t)pos0 * nsq + rho) * (16 * CH) + ch0 + 4 * q] = acc[j];
+            if (j < my_tiles) {
+                const int p = rho / nsq, sq = rho - p * nsq;
+                lds4[p * PP4 + sq * CP4 + (ch0 >> 2) + q] = acc[j];
             }
+            acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         }
-        return;
+        TG_STAMP(0, 4);
+        __syncthreads();
+        TG_STAMP(0, 5);
     }
-    TG_STAMP(0, 2);
-    __syncthreads();  // every wave has finished reading the input planes
-    TG_STAMP(0, 3);
-    // the square-tile image replaces them.  Every cell of all PW positions is written: the rows of a ragged workgroup's missing
-    // positions read the zero row in layer 0, so their cells hold finite values (bias, ReLU) that later layers read and never store
-#pragma unroll
-    for (int j = 0; j < RTW; j++) {
-        const int rho = rho0 + j * 16;
-        if (j < my_tiles) {
-            const int p = rho / nsq, sq = rho - p * nsq;
-            lds4[p * PP4 + sq * CP4 + (ch0 >> 2) + q] = acc[j];
-        }
-        acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
-    TG_STAMP(0, 4);
-    __syncthreads();
-    TG_STAMP(0, 5);
 
-    // ---- layers 1 … : this lane's tile column is position r16 ----
-    int ad = r16 * PP4 + q;
-    const int turn = rg;  // waves w and w + 4 share a SIMD
+    // ---- layers 1 … ----
     for (int layer = 1; layer < T.nlayers; layer++) {
         // (the address is the same in every layer, but the compiler must not know: it would hoist the (address + offset) sums of
         // the main loop out of the layer loop and spill them instead of using ds_read immediates)
@@ -2134,7 +2229,10 @@ static hipError_t launch_tower_sq_t(hipStream_t st, const float* in, const Tower
     const size_t plain = (size_t)(PW * NB * NB + 1) * ((CB ? T.cb_cin_pad : T.cin_pad) + LDS_PAD16) * sizeof(float) +
                          (CB ? tower_cb_table_bytes(PW, 16 * CH) : 0);
     const size_t image = (size_t)PW * sq_image_pitch4<CH>() * 16;  // 115 200 B
-    const size_t lds = plain > image ? plain : image;
+    // CB: layer 0 runs on the square-tile image too, PB behind it (152 064 B); its loop is built for 32 board channels, 3 real MFMAs
+    // in the last chunk
+    if (CB && (T.cb_cin_pad != 32 || T.cb_last_t != 3)) return hipErrorInvalidValue;
+    const size_t lds = CB ? image + tower_cb_table_bytes(PW, 16 * CH) : plain > image ? plain : image;
     static LdsAttr lds_attr;
     if (hipError_t e = lds_attr.ensure((const void*)k_tower_sq<CH0, FROM_STATES, CB>, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((k_tower_sq<CH0, FROM_STATES, CB>), dim3((B + PW - 1) / PW), dim3(512), lds, st, in, T, out, B);
