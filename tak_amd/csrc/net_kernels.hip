@@ -35,7 +35,7 @@
 #include "conv_mainloop.cuh"
 #include "fc_ring.cuh"
 #include "softmax.cuh"
-#include "tower_cb.cuh"
+#include "tower_stage.cuh"
 #include "kernels.h"
 
 namespace tg {
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_conv_pos(const float* __restric
             size_t o = ((size_t)pos0 * nsq + rho) * out_stride + ch;
             f32x4 v = acc[j] + bv;
             if (res) v += *(const f32x4*)&res[o];
-            if (relu) { v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f); }
+            if (relu) v = relu4(v);
             if (ch + 3 < cout_valid) *(f32x4*)&out[o] = v;
             else for (int t = 0; t < 4; t++) if (ch + t < cout_valid) out[o + t] = v[t];
         }
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_conv_pos(const float* __restric
 // tiles it produces).  Only the input planes are read from HBM and only the final activations are
 // written (for the policy / value heads); per layer the only global traffic is the L2-resident weights.
 // ------------------------------------------------------------------------------------------------
-// ---- constant input planes as a per-position bias (TowerParams.cb; states entry of the fused towers; tower_cb.cuh) ----
+// ---- constant input planes as a per-position bias (TowerParams.cb; states entry of the fused towers; tower_stage.cuh) ----
 // Stages what layer 0 needs for the positions of one workgroup: the 26 / 28 BOARD planes of every square as a plain image of
 // 32 channels per row (last chunk permuted for cb_last_t = 3), and the table PB[position][border class][F].
 template <int NWAVES>
@@ -498,9 +498,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_tower(const float* __restrict__
         const f32x4 bv = *(const f32x4*)&T.b[layer][ch0 + 4 * q];
 #pragma unroll
         for (int j = 0; j < RTW; j++) {
-            f32x4 v = acc[j] + ((CB && layer == 0) ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 >> 2) + q)] : bv);
-            v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
-            acc[j] = v;
+            acc[j] = relu4(acc[j] + ((CB && layer == 0) ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 >> 2) + q)] : bv));
         }
         if (layer + 1 == T.nlayers) {
 #pragma unroll
@@ -545,7 +543,8 @@ __global__ __launch_bounds__(NWAVES * 64) void k_tower(const float* __restrict__
 // The fused tower for SMALL batches of wide networks (round 6): k_tower gives every position to one workgroup — at the reference's
 // own constants (32 lock-step games → 32 leaves per forward, Net6 = 16 blocks × 128 filters; train/src/self_play.rs:94,
 // alpha-tak/src/model/net6.rs:16-17) that is 32 busy CUs of 256, each issuing 8 channel tiles × 3 row tiles × 288 MFMAs per layer
-// (23 µs per layer, 882 µs per forward).  Here a position is SPLIT over G = F / 16 workgroups by output channel tile: workgroup
+// (23 µs per layer, 882 µs per forward).  Here a position is SPLIT over G = F / 16 workgroups by output channel tile (G = 8 at
+// F = 128, G = 4 at F = 64: the two that launch_tower_split instantiates): workgroup
 // (position p, group g) holds the whole input image of p in LDS and computes CTW channel tiles × NRT row tiles, one (row tile, channel
 // tile) pair per wave = ONE chain of 9·16·CH/4 MFMAs — the shortest critical path the arithmetic allows (a chain cannot be cut: every
 // output element is accumulated over k in k_tower's order, so the results are bit-identical).  Between two layers the G workgroups of a
@@ -671,8 +670,7 @@ __global__ __launch_bounds__(NRT * CTW * 64) void k_tower_split(const uint8_t* _
             conv_mainloop_tile<2, 3>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho, q, vmask[0], acc, wf0);
         } else conv_mainloop_tile<CH>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho, q, vmask[0], acc, wf);
         TG_STAMP(layer, 1);
-        f32x4 v = acc + (layer == 0 ? pb4[tower_cb_index(rho, rows, n, nsq, F4, (ch0 >> 2) + q)] : bv);
-        v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
+        const f32x4 v = relu4(acc + (layer == 0 ? pb4[tower_cb_index(rho, rows, n, nsq, F4, (ch0 >> 2) + q)] : bv));
         if (layer + 1 == T.nlayers) {
             if (rho < rows) {
                 if (T.frag_out) ((f32x4*)out)[((size_t)(p >> 4) * (nsq * CH) + rho * CH + (ch0 >> 4)) * 64 + (p & 15) * 4 + q] = v;
@@ -856,9 +854,7 @@ __device__ __forceinline__ void tower_plain_layer0(const float* __restrict__ in,
     const f32x4 bv = *(const f32x4*)&T.b[0][ch0 + 4 * q];
 #pragma unroll
     for (int j = 0; j < RTW; j++) {
-        f32x4 v = acc[j] + (CB ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 >> 2) + q)] : bv);
-        v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
-        acc[j] = v;
+        acc[j] = relu4(acc[j] + (CB ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 >> 2) + q)] : bv));
     }
     rho0_out = rho0;
     my_tiles_out = my_tiles;
@@ -940,11 +936,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_tower_halo(const float* __restr
         }
         TG_STAMP(layer, 1);
 #pragma unroll
-        for (int j = 0; j < RTW; j++) {
-            f32x4 v = acc[j] + bv;
-            v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
-            acc[j] = v;
-        }
+        for (int j = 0; j < RTW; j++) acc[j] = relu4(acc[j] + bv);
         if (layer + 1 == T.nlayers) {
 #pragma unroll
             for (int j = 0; j < RTW; j++)
@@ -1017,9 +1009,7 @@ __device__ __forceinline__ void tower_sq_cb_epilogue(const f32x4* pbq, f32x4 (&a
         constexpr int n = SQ_NB;
         const int sq = sq_tile(RG, j), y = sq / n, x = sq % n;
         const int cls = (y == 0 ? 0 : y == n - 1 ? 2 : 1) * 3 + (x == 0 ? 0 : x == n - 1 ? 2 : 1);  // tower_cb_index
-        f32x4 v = acc[j] + pbq[cls * 4 * CH];
-        v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
-        acc[j] = v;
+        acc[j] = relu4(acc[j] + pbq[cls * 4 * CH]);
     }
 }
 
@@ -1127,11 +1117,7 @@ __global__ __launch_bounds__(512) void k_tower_sq(const float* __restrict__ in, 
         else conv_mainloop_sq<1, CH>(img4, T.w[layer], wnext, wlane, acc, turn, w0, w1);
         TG_STAMP(layer, 1);
 #pragma unroll
-        for (int j = 0; j < RTW; j++) {
-            f32x4 v = acc[j] + bv;
-            v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
-            acc[j] = v;
-        }
+        for (int j = 0; j < RTW; j++) acc[j] = relu4(acc[j] + bv);
         if (layer + 1 == T.nlayers) {
             if (r16 < npos) {
                 // (opaque to the compiler, like the image address: it would otherwise compute all 2 × 13 64-bit store addresses
@@ -1269,7 +1255,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_conv_halo(const float* __restri
             const size_t o = ((size_t)pos0 * nsq + rowid[j]) * out_stride + ch;
             f32x4 v = acc[j] + bv;
             if (res) v += *(const f32x4*)&res[o];
-            if (relu) { v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f); }
+            if (relu) v = relu4(v);
             if (ch + 3 < cout_valid) *(f32x4*)&out[o] = v;
             else for (int t = 0; t < 4; t++) if (ch + t < cout_valid) out[o + t] = v[t];
             if (stats_part && !bnb.y) {
@@ -1352,7 +1338,7 @@ __global__ __launch_bounds__(NRT * 64) void k_conv_split(const float* __restrict
     const int ch = ch0 + 4 * q;
     if (rho < rows && ch < cout_valid) {
         f32x4 v = acc + *(const f32x4*)&bias[ch];
-        if (relu) { v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f); }
+        if (relu) v = relu4(v);
         const size_t o = ((size_t)p * nsq + rho) * out_stride + ch;
         if (ch + 3 < cout_valid) *(f32x4*)&out[o] = v;
         else for (int t = 0; t < 4; t++) if (ch + t < cout_valid) out[o + t] = v[t];
@@ -2318,7 +2304,8 @@ static hipError_t launch_tower_split_t(hipStream_t st, const uint8_t* states, co
     return hipGetLastError();
 }
 
-// small batches of the 128-filter networks: a position split over 8 / 4 / 2 workgroups by channel tile (k_tower_split; identical bits);
+// small batches of wide networks: a position split over G workgroups by channel tile — G = 8 at 128 filters, G = 4 at 64 on 5×5, the
+// only two that exist (k_tower_split; identical bits);
 // scratch = TowerParams.split_buf's two exchange buffers
 static bool launch_tower_split(hipStream_t st, const uint8_t* states, const TowerParams& T, float* out, float* scratch, int B, int n,
                                hipError_t* err) {

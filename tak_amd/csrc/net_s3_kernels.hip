@@ -30,7 +30,7 @@
 #include "conv_mainloop.cuh"
 #include "softmax.cuh"
 #include "fc_ring.cuh"
-#include "tower_cb.cuh"
+#include "tower_stage.cuh"
 #include "kernels.h"
 
 
@@ -223,7 +223,7 @@ __device__ __forceinline__ void s3_mainloop_halo(const u32x4* __restrict__ lds4,
 // RTW: row tiles of a full row group; NRG row groups × NCG channel groups (of 2 tiles) = NW waves.  With NW = 4 two
 // workgroups share a CU (one wave of each per SIMD): they drift apart, so one's epilogue / barrier phases overlap the other's MFMAs.
 // (the second launch bound caps the 4-wave variant at 256 registers so that two of its workgroups fit on a CU)
-// CB (with FROM_STATES, KC0 = 1): layer 0 over the board planes only, the constant planes as the per-position bias PB (tower_cb.cuh)
+// CB (with FROM_STATES, KC0 = 1): layer 0 over the board planes only, the constant planes as the per-position bias PB (tower_stage.cuh)
 template <int RTW, int KC0, int KC, bool FROM_STATES, bool OUT_SPLIT, int NW, bool CB = false>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_tower_s3(const void* __restrict__ in, TowerS3Params T, float* __restrict__ out, int B, int n,
                                                   int PW, int NCG, int pad0) {
@@ -357,9 +357,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_tower_s3(const voi
             const f32x4 bv = *(const f32x4*)&T.b[layer][ch0 + 8 * q + 4 * t];
 #pragma unroll
             for (int j = 0; j < RTW; j++) {
-                f32x4 v = acc[j][t] + ((CB && layer == 0) ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 + 8 * q + 4 * t) >> 2)] : bv);
-                v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
-                acc[j][t] = v;
+                acc[j][t] = relu4(acc[j][t] + ((CB && layer == 0) ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 + 8 * q + 4 * t) >> 2)] : bv));
             }
         }
         if (layer + 1 == T.nlayers && !OUT_SPLIT) {
@@ -588,9 +586,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_tower_s3_halo(cons
             const f32x4 bv = *(const f32x4*)&T.b[0][ch0 + 8 * q + 4 * t];
 #pragma unroll
             for (int j = 0; j < RTW; j++) {
-                f32x4 v = acc[j][t] + (CB ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 + 8 * q + 4 * t) >> 2)] : bv);
-                v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
-                acc[j][t] = v;
+                acc[j][t] = relu4(acc[j][t] + (CB ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 + 8 * q + 4 * t) >> 2)] : bv));
             }
         }
         TG_S3_STAMP(0, 2);
@@ -655,9 +651,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_tower_s3_halo(cons
         for (int t = 0; t < 2; t++) {
 #pragma unroll
             for (int j = 0; j < RTW; j++) {
-                f32x4 v = acc[j][t] + bv[t];
-                v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
-                acc[j][t] = v;
+                acc[j][t] = relu4(acc[j][t] + bv[t]);
             }
         }
         if (layer + 1 == T.nlayers && !OUT_SPLIT) {

@@ -1,5 +1,7 @@
-// tower_cb.cuh — the constant input planes of game_repr as a per-position bias of layer 0 (TowerParams.cb / TowerS3Params.cb),
-// shared by the exact-f32 towers (net_kernels.hip) and the split-bf16 towers (net_s3_kernels.hip).
+// tower_stage.cuh — what the fused towers share around their main loops: the exact-f32 towers (net_kernels.hip: k_tower, k_tower_halo,
+// k_tower_sq, k_tower_split) and the split-bf16 towers (net_s3_kernels.hip: k_tower_s3, k_tower_s3_halo) differ in their LDS image and
+// their main loop.  Here: the constant planes of game_repr as a per-position bias of layer 0 (TowerParams.cb / TowerS3Params.cb), and
+// the ReLU on a quad of every epilogue.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,4 +67,9 @@ __device__ __forceinline__ int tower_cb_index(int rho, int rows, int n, int nsq,
     return (p * 9 + cls) * F4 + chq;
 }
 
+// ---- epilogue: ReLU on a quad ----
+__device__ __forceinline__ f32x4 relu4(f32x4 v) {
+    v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f);
+    return v;
+}
 }  // namespace tg
