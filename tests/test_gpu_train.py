@@ -92,8 +92,11 @@ def test_forward_training_vs_torch(orc, n, blocks, filters, head, count):
     e.close()
 
 
-@pytest.mark.parametrize("n,blocks,filters,head,count", CASES)
-def test_chunk_gradients_vs_autograd(orc, n, blocks, filters, head, count):
+def chunk_gradients_against_fp64(orc, n, blocks, filters, head, count):
+    """The gradient gate of the training step on one topology and chunk size (shared with tests/test_gpu_train_brackets.py and
+    scripts/train_config_sweep.py): two accumulated chunks of `count` examples; losses to relative 1e-5; every tensor against
+    torch_ref.fp64_gradients under torch_ref.engine_relu_decisions to 2e-5; the looser PyTorch-f32 sanity bound; Σ policy.bias
+    gradient = 0 on the FC head.  → (worst tensor, its relative distance to fp64)"""
     net = torch_ref.make_net(n, blocks, filters, head, seed=10 + n)
     e = _engine(n, blocks, filters, head)
     e.load_state_dict(torch_ref.abi_tensors(net))
@@ -140,6 +143,12 @@ def test_chunk_gradients_vs_autograd(orc, n, blocks, filters, head, count):
         gb = e.train_get_grad("policy.bias", shapes["policy.bias"])
         assert abs(float(gb.astype(np.float64).sum())) <= 1e-5
     e.close()
+    return worst
+
+
+@pytest.mark.parametrize("n,blocks,filters,head,count", CASES)
+def test_chunk_gradients_vs_autograd(orc, n, blocks, filters, head, count):
+    chunk_gradients_against_fp64(orc, n, blocks, filters, head, count)
 
 
 def test_steps_track_torch_adam(orc):

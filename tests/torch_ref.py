@@ -141,12 +141,15 @@ def named_grads(net):
     return {abi_name(k): v.grad.detach().numpy().copy() for k, v in net.named_parameters()}
 
 
-def fp64_gradients(net, planes, pi, z, mask_sets, verbose=False):
+def fp64_gradients(net, planes, pi, z, mask_sets, verbose=False, hook=None):
     """fp64 forward of train_inner's loss (network.rs:58-91) on a copy of `net`, then one backward pass per entry of mask_sets:
     None = the fp64 network's own ReLU decisions, a float t = the decisions taken at y > t, a list of 1 + 2·blocks bool tensors
     [B, F, n, n] = THOSE decisions (layer order conv0, res0.conv1, res0.conv2, …).  The backward pass of a ReLU network is the exact
     derivative of a piecewise-linear function once the decisions are fixed, and the forward pass takes them: with an
     implementation's own decisions on the reference side its gradients have to agree to rounding, with no allowance for "flips".
+    hook (tests/test_train_gates.py: how a deliberately wrong operation is put on the reference side) may replace operations of the
+    fp64 network: {"conv": f(layer, module, x) → z, "bn": f(layer, module, z) → BatchNorm output, "policy": f(module, x) → logits}
+    with layer = 0 for conv0 / bn0, 1 + 2·i and 2 + 2·i for block i; an absent entry is the module itself.
     → ([{ABI name: gradient}], [pre-activation of every ReLU, float64 tensors])"""
     import copy
 
@@ -179,12 +182,16 @@ def fp64_gradients(net, planes, pi, z, mask_sets, verbose=False):
         pres.append(t.detach())
         return Relu.apply(t, len(pres) - 1)
 
-    s = relu(n64.bn0(n64.conv0(x)))
-    for blk in n64.res:  # res_block.rs:13-24
-        y = relu(blk.bn1(blk.conv1(s)))
-        s = relu(blk.bn2(blk.conv2(y)) + s)
+    hook = hook or {}
+    conv = hook.get("conv", lambda layer, m, t: m(t))
+    bn = hook.get("bn", lambda layer, m, t: m(t))
+    policy = hook.get("policy", lambda m, t: m(t))
+    s = relu(bn(0, n64.bn0, conv(0, n64.conv0, x)))
+    for i, blk in enumerate(n64.res):  # res_block.rs:13-24
+        y = relu(bn(2 * i + 1, blk.bn1, conv(2 * i + 1, blk.conv1, s)))
+        s = relu(bn(2 * i + 2, blk.bn2, conv(2 * i + 2, blk.conv2, y)) + s)
     flat = s.reshape(s.shape[0], -1)
-    logits = n64.policy(flat) if n64.head == "fc5" else n64.policy(s).reshape(s.shape[0], -1)
+    logits = policy(n64.policy, flat) if n64.head == "fc5" else policy(n64.policy, s).reshape(s.shape[0], -1)
     logp = torch.log_softmax(logits, dim=1)
     v = torch.tanh(n64.value(flat))
     b = x.shape[0]
