@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
 """Did a change move any kernel?  Compare the device code of two source trees, kernel by kernel.
 
-    python scripts/kernel_isa_diff.py A B [--only net_kernels.hip ...] [--jobs 8] [--show 20]
+    python scripts/kernel_isa_diff.py A B [--only tower_kernels.hip ...] [--jobs 8] [--show 20]
 
 A and B are directories that hold tak_amd/csrc/, or git revisions of this repository (exported with `git archive` into a
 temporary directory; `.` and paths are taken as directories first).  Every tak_amd/csrc/*.hip of each tree is compiled
 device-only with that tree's Makefile FLAGS (+ --cuda-device-only --no-gpu-bundle-output -c: an AMDGPU ELF that llvm-objdump
 reads), disassembled and split per symbol with addresses and encodings dropped; the kernel descriptors (VGPR / AGPR / SGPR
-counts, LDS and private-segment size, ...) come from `llvm-readelf --notes`.  Per symbol one line: same / differs / only in A /
-only in B; then a summary line.  Exit status 0 only if every symbol of every file is `same`.  Needs hipcc and no GPU.
+counts, LDS and private-segment size, ...) come from `llvm-readelf --notes`.  A symbol is compared wherever it lives: the two
+trees are paired by symbol name over all their compiled files, not per file name, so a kernel that moved to another translation
+unit is `same` if its text and descriptor are; the line names the file on both sides.  A symbol that one tree emits from two
+files is `twice`, a failure of its own.  What llvm-objdump prints behind a symbol's last instruction — the zero fill up to the next
+symbol's alignment (`...`), the s_nop / s_code_end padding behind the last symbol of .text — is dropped: it belongs to the symbol's
+place in its file, not to the kernel, and differs as soon as a kernel has another neighbour.  --only is applied per tree to the
+files that exist there.  Per symbol one line: same / differs / only in A / only in B / twice; then a summary line.  Exit status 0
+only if every symbol is `same`.  Needs hipcc and no GPU.
 """
 import argparse
 import concurrent.futures
@@ -69,6 +75,11 @@ def disassembly(obj):
         line = line.split("//")[0].strip()  # the trailing comment holds address and encoding
         if cur is not None and line:
             cur.append(line)
+    # what the assembler puts behind a symbol's last instruction belongs to its place in the file, not to it: the zero fill up to
+    # the next symbol's alignment (`...`) and the s_nop / s_code_end padding behind the last symbol of the section
+    for text in syms.values():
+        while text and text[-1] in ("...", "s_nop 0", "s_code_end"):
+            text.pop()
     return syms
 
 
@@ -104,49 +115,61 @@ def build_tree(tree, outdir, only, jobs):
     os.makedirs(outdir, exist_ok=True)
     with concurrent.futures.ThreadPoolExecutor(jobs) as pool:
         objs = list(pool.map(lambda n: compile_device(csrc, n, outdir, flags), names))
-    return {n: (disassembly(o), descriptors(o)) for n, o in zip(names, objs)}
+    syms, twice = {}, {}  # symbol → (file, instructions, descriptor or None); symbol → every file that emits it
+    for n, o in zip(names, objs):
+        desc = descriptors(o)
+        for sym, text in disassembly(o).items():
+            if sym in syms:
+                twice.setdefault(sym, [syms[sym][0]]).append(n)
+            else:
+                syms[sym] = (n, text, desc.get(sym))
+    return names, syms, twice
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("a")
     ap.add_argument("b")
-    ap.add_argument("--only", nargs="*", default=[], help="file names under tak_amd/csrc to compare (default: every *.hip)")
+    ap.add_argument("--only", nargs="*", default=[], help="file names under tak_amd/csrc to compare, where a tree has them (default: every *.hip)")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--show", type=int, default=0, help="lines of unified diff to print for a symbol that differs")
     ap.add_argument("--quiet", action="store_true", help="print only the symbols that are not `same`, and the summary")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="kernel_isa_diff_") as tmp:
-        A = build_tree(resolve_tree(args.a, tmp), os.path.join(tmp, "obj_a"), args.only, args.jobs)
-        B = build_tree(resolve_tree(args.b, tmp), os.path.join(tmp, "obj_b"), args.only, args.jobs)
-    count = {"same": 0, "differs": 0, "only in A": 0, "only in B": 0}
+        files_a, A, twice_a = build_tree(resolve_tree(args.a, tmp), os.path.join(tmp, "obj_a"), args.only, args.jobs)
+        files_b, B, twice_b = build_tree(resolve_tree(args.b, tmp), os.path.join(tmp, "obj_b"), args.only, args.jobs)
+    count = {"same": 0, "differs": 0, "only in A": 0, "only in B": 0, "twice": 0}
     kernels = 0
-    for name in sorted(set(A) | set(B)):
-        (ta, da), (tb, db) = A.get(name, ({}, {})), B.get(name, ({}, {}))
-        for sym in sorted(set(ta) | set(tb)):
-            if sym not in tb:
-                verdict = "only in A"
-            elif sym not in ta:
-                verdict = "only in B"
-            else:
-                what = []
-                if ta[sym] != tb[sym]:
-                    what.append(f"text ({len(ta[sym])} → {len(tb[sym])} instructions)")
-                what += [f"{k} {da[sym].get(k)} → {db[sym].get(k)}" for k in DESCRIPTOR_KEYS
-                         if sym in da and sym in db and da[sym].get(k) != db[sym].get(k)]
-                if (sym in da) != (sym in db):
-                    what.append("kernel descriptor on one side only")
-                verdict = "differs" if what else "same"
-            count[verdict] += 1
-            kernels += sym in da or sym in db
-            if verdict != "same" or not args.quiet:
-                print(f"{verdict:9s} {name} {sym}" + (": " + "; ".join(what) if verdict == "differs" else ""))
-            if verdict == "differs" and args.show:
-                for line in list(difflib.unified_diff(ta[sym], tb[sym], "A", "B", lineterm="", n=2))[: args.show]:
-                    print("    " + line)
+    for sym in sorted(set(A) | set(B)):
+        what = []
+        if sym in twice_a or sym in twice_b:
+            verdict = "twice"
+            what = [f"{side} emits it from {' and '.join(t[sym])}" for side, t in (("A", twice_a), ("B", twice_b)) if sym in t]
+        elif sym not in B:
+            verdict = "only in A"
+        elif sym not in A:
+            verdict = "only in B"
+        else:
+            (_, ta, da), (_, tb, db) = A[sym], B[sym]
+            if ta != tb:
+                what.append(f"text ({len(ta)} → {len(tb)} instructions)")
+            if da is not None and db is not None:
+                what += [f"{k} {da.get(k)} → {db.get(k)}" for k in DESCRIPTOR_KEYS if da.get(k) != db.get(k)]
+            elif (da is None) != (db is None):
+                what.append("kernel descriptor on one side only")
+            verdict = "differs" if what else "same"
+        count[verdict] += 1
+        fa, fb = (A[sym][0] if sym in A else None), (B[sym][0] if sym in B else None)
+        kernels += (sym in A and A[sym][2] is not None) or (sym in B and B[sym][2] is not None)
+        if verdict != "same" or not args.quiet:
+            where = fa if fa == fb else f"{fa} → {fb}" if fa and fb else fa or fb
+            print(f"{verdict:9s} {where} {sym}" + (": " + "; ".join(what) if what else ""))
+        if verdict == "differs" and args.show:
+            for line in list(difflib.unified_diff(A[sym][1], B[sym][1], "A", "B", lineterm="", n=2))[: args.show]:
+                print("    " + line)
     total = sum(count.values())
-    print(f"{len(set(A) | set(B))} files, {total} symbols ({kernels} kernels): {count['same']} same, {count['differs']} differ, "
-          f"{count['only in A']} only in A, {count['only in B']} only in B")
+    print(f"{len(files_a)} → {len(files_b)} files, {total} symbols ({kernels} kernels): {count['same']} same, {count['differs']} differ, "
+          f"{count['only in A']} only in A, {count['only in B']} only in B, {count['twice']} twice")
     return 0 if count["same"] == total and total > 0 else 1
 
 

@@ -8,7 +8,8 @@
 #include <cstdio>
 #include <vector>
 #include <algorithm>
-#include "../../tak_amd/csrc/net_kernels.hip"
+#include "../../tak_amd/csrc/conv_kernels.hip"
+#include "../../tak_amd/csrc/tower_kernels.hip"  // tower_halo_geometry, tower_halo_slotmap
 #include "probe_env.h"
 using namespace tg;
 int main(int argc, char** argv) {

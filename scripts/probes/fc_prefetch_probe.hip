@@ -8,7 +8,7 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -I tak_amd/csrc scripts/probes/fc_prefetch_probe.hip -o scripts/probes/_bin/fc_prefetch_probe
 #include <cstdio>
 #include <vector>
-#include "../../tak_amd/csrc/net_kernels.hip"
+#include "../../tak_amd/csrc/fc_kernels.hip"
 #include "probe_env.h"
 using namespace tg;
 

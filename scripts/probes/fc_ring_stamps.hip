@@ -1,11 +1,11 @@
-// Where a K-step of k_fc_ring goes, wave by wave: builds net_kernels.hip with -DTG_TOWER_STAMPS (TG_STAMP in the kernel: top of a step,
+// Where a K-step of k_fc_ring goes, wave by wave: builds fc_kernels.hip with -DTG_TOWER_STAMPS (TG_STAMP in the kernel: top of a step,
 // after the wait for ready[], before / after the mid-step s_waitcnt vmcnt(0), after the wait for done[], after the refill's LDS-DMA issue,
 // end of the step) and prints, for workgroup 0 of a C2-shaped launch (4096 rows, K = 1600, logits rows), the s_memtime deltas summed
 // over the 25 steps of every wave.
 // hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DTG_TOWER_STAMPS scripts/probes/fc_ring_stamps.hip -o scripts/probes/_bin/fc_ring_stamps
 #include <cstdio>
 #include <vector>
-#include "../../tak_amd/csrc/net_kernels.hip"
+#include "../../tak_amd/csrc/fc_kernels.hip"
 #include "probe_env.h"
 using namespace tg;
 int main() {

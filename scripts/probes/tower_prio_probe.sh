@@ -4,5 +4,5 @@
 set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 for d in "$@"; do
-  EXTRA_DEFS="$d" bash $R/scripts/probes/fc_ring_probe.sh "0" 2>&1 | grep "^mask" | sed "s/^mask 0/[$d]/; s/ | k_softmax.*//"
+  UNIT=tower_kernels EXTRA_DEFS="$d" bash $R/scripts/probes/fc_ring_probe.sh "0" 2>&1 | grep "^mask" | sed "s/^mask 0/[$d]/; s/ | k_softmax.*//"
 done

@@ -2,7 +2,7 @@
 // one workgroup of a 4096-position launch, the s_memtime deltas between the phase boundaries of every layer and wave:
 // main loop | bias + ReLU | wait at barrier 1 | skip read + split + write-back | wait at barrier 2.
 // usage: tower_s3_stamps [c2|c5|c3]
-// hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DTG_S3_STAMPS -I../../tak_amd/csrc tower_s3_stamps.hip ../../tak_amd/csrc/net_kernels.hip -o _bin/tower_s3_stamps
+// hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DTG_S3_STAMPS -I../../tak_amd/csrc tower_s3_stamps.hip ../../tak_amd/csrc/tower_kernels.hip ../../tak_amd/csrc/fc_kernels.hip -o _bin/tower_s3_stamps
 #include <cstdio>
 #include <cstring>
 #include <vector>

@@ -4,7 +4,7 @@
 // hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DTG_TOWER_STAMPS -I../../tak_amd/csrc tower_small_stamps.hip -o _bin/tower_small_stamps
 #include <cstdio>
 #include <vector>
-#include "../../tak_amd/csrc/net_kernels.hip"
+#include "../../tak_amd/csrc/tower_kernels.hip"
 #include "probe_env.h"
 using namespace tg;
 int main(int argc, char** argv) {

@@ -1,10 +1,10 @@
-// Where a layer of the fused tower spends its cycles: builds net_kernels.hip with -DTG_TOWER_STAMPS and prints, for
+// Where a layer of the fused tower spends its cycles: builds tower_kernels.hip with -DTG_TOWER_STAMPS and prints, for
 // workgroup 0 of a C2-shaped launch (4096 positions, 6 blocks × 64 filters), the s_memtime deltas between the phase
 // boundaries of every layer and wave: main loop | epilogue VALU | wait at barrier 1 | LDS write-back | wait at barrier 2.
 // hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DTG_TOWER_STAMPS -I../../tak_amd/csrc tower_stamps.hip -o _bin/tower_stamps
 #include <cstdio>
 #include <vector>
-#include "../../tak_amd/csrc/net_kernels.hip"
+#include "../../tak_amd/csrc/tower_kernels.hip"
 #include "probe_env.h"
 using namespace tg;
 int main(int argc, char** argv) {

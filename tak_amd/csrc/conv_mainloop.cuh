@@ -144,6 +144,53 @@ __device__ __forceinline__ void conv_mainloop(const f32x4* __restrict__ lds4, co
     }
 }
 
+// one (row tile, channel tile) pair: the products of conv_mainloop<1, CHL> in the same order (tap, chunk, t); weights one tap ahead,
+// the tap's activation quads one tap ahead as well.  w0 = the first tap's CHL weight quads, requested by the caller (conv_tile_first_weights)
+// as early as it likes — they depend on nothing but the layer.  TAPCHAIN: every tap's products in a chain of their own that is added
+// to acc when the tap is complete (k_conv_pos / conv_mainloop_halo<SPLIT>: the stand-alone layers' order).
+template <int CHL>
+__device__ __forceinline__ void conv_tile_first_weights(const f32x4* __restrict__ wp, size_t wstride4, f32x4 (&w0)[CHL]) {
+#pragma unroll
+    for (int kc = 0; kc < CHL; kc++) w0[kc] = wp[(size_t)kc * wstride4];
+}
+template <int CHL, int LAST_T = 4, bool TAPCHAIN = false>
+__device__ __forceinline__ void conv_mainloop_tile(const f32x4* __restrict__ lds4, const f32x4* __restrict__ wp, size_t wstride4, int LS4,
+                                                   int rows, int n, int rho, int q, int vmask, f32x4& acc, const f32x4 (&w0)[CHL]) {
+    // LAST_T < 4 (layer 0): the last chunk's real channels fill MFMAs t < LAST_T, the others would multiply padding (conv_mainloop)
+    const int zero4 = rows * LS4 + q, base = rho * LS4 + q;
+    auto tap_addr = [&](int tap) { return ((vmask >> tap) & 1) ? base + ((tap / 3 - 1) * n + (tap % 3 - 1)) * LS4 : zero4; };
+    f32x4 w[2][CHL], a[2][CHL];
+#pragma unroll
+    for (int kc = 0; kc < CHL; kc++) w[0][kc] = w0[kc];
+    {
+        const int a0 = tap_addr(0);
+#pragma unroll
+        for (int kc = 0; kc < CHL; kc++) a[0][kc] = lds4[a0 + kc * 4];
+    }
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) {
+        const int cur = tap & 1, nxt = cur ^ 1;
+        if (tap + 1 < 9) {
+#pragma unroll
+            for (int kc = 0; kc < CHL; kc++) w[nxt][kc] = wp[(size_t)((tap + 1) * CHL + kc) * wstride4];
+            const int a1 = tap_addr(tap + 1);
+#pragma unroll
+            for (int kc = 0; kc < CHL; kc++) a[nxt][kc] = lds4[a1 + kc * 4];
+        }
+        // (left alone hipcc sinks every load next to its use: the chain would then wait out an L2 round trip per chunk)
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 part = TAPCHAIN ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : acc;
+#pragma unroll
+        for (int kc = 0; kc < CHL; kc++)
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+                if (kc + 1 < CHL || t < LAST_T) part = __builtin_amdgcn_mfma_f32_16x16x4f32(w[cur][kc][t], a[cur][kc][t], part, 0, 0, 0);
+        if (TAPCHAIN) acc += part;
+        else acc = part;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // The same loop over the HALO image (k_tower_halo, layers ≥ 1).  Every board row is stored with one zero cell behind
 // it and every position with a zero row (+ 1 cell) behind it, so a tap is the same cell offset for every square of

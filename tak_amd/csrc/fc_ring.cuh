@@ -1,4 +1,4 @@
-// fc_ring.cuh — what the two ring FCs (k_fc_ring in net_kernels.hip: exact f32; k_fc_s3_ring in net_s3_kernels.hip: split bf16) share:
+// fc_ring.cuh — what the two ring FCs (k_fc_ring in fc_kernels.hip: exact f32; k_fc_s3_ring in net_s3_kernels.hip: split bf16) share:
 // the dealing of the leftover tiles, the gather target, the LDS flag primitives.  Tile and statistics geometry: softmax.cuh.
 #pragma once
 #include <hip/hip_runtime.h>

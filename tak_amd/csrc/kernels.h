@@ -43,7 +43,7 @@ void launch_perft_count(hipStream_t st, const uint8_t* states, int count, int n,
 void launch_perft_expand(hipStream_t st, const uint8_t* states, int count, int n, const int64_t* offsets, const int32_t* root_of,
                          uint8_t* next_states, int32_t* next_root);
 
-// net_kernels.hip
+// conv_kernels.hip
 // stats_part / stats_blocks (optional, training forward): when the launch can emit BatchNorm's column sums from its
 // accumulators (the halo kernel, all channels in one workgroup column) it writes *stats_blocks partial rows
 // part[(block·2 + {Σ, Σ²})·CoutP + channel] as doubles and sets *stats_blocks > 0; otherwise *stats_blocks = 0 and the caller
@@ -59,6 +59,7 @@ hipError_t launch_conv3x3(hipStream_t st, const float* in, const float* Wp, cons
 // mean, 1/σ and the running statistics from such partial rows (Σz, Σz² in double): replaces launch_bn_stats' two passes over z
 hipError_t launch_bn_stats_from_partials(hipStream_t st, const double* part, int nblk, int M, int F, float eps, float momentum,
                                          float* mean, float* invstd, float* running_mean, float* running_var);
+// tower_kernels.hip
 // fused residual tower (k_tower): per-layer weight / bias pointers
 struct TowerParams {
     const float* w[48];   // per layer: Wp[K/16][CoutP][16]
@@ -137,8 +138,9 @@ struct FcGatherArgs;
 hipError_t launch_fc_s3(hipStream_t st, const float* act_split, const void* Wp, const void* Wr, const float* bias, float* out, int M, int K, int NP,
                         int out_stride, int n_valid, float* stats = nullptr, int n_soft = 0, const FcGatherArgs* gather = nullptr);
 bool fc_s3_ring_supported(int M, int K, int n_valid);
-hipError_t launch_fc_stats(hipStream_t st, const float* logits, int ld, int M, int n_soft, float* stats);  // softmax.cuh's statistics of logits in memory
+hipError_t launch_fc_stats(hipStream_t st, const float* logits, int ld, int M, int n_soft, float* stats);  // fc_kernels.hip: softmax.cuh's statistics of logits in memory
 hipError_t launch_value_head_s3(hipStream_t st, const float* act_split, const float* wv, float bv, int B, int len, float* eval);
+// fc_kernels.hip
 // a_frag: A is in the fragment-major order of TowerParams.frag_out (needs fc_frag_supported(K, NP))
 // stats (optional, needs fc_stats_supported): the block-wise softmax statistics of softmax.cuh over columns < n_soft,
 // [M][FC_STAT_STRIDE][2] floats (11 block pairs, then {value pre-activation = column n_soft, 0}) — emitted by the FC's epilogue

@@ -6,7 +6,7 @@
 // pipe runs 16× the f32 MFMA rate per MAC, so three passes cost 3/16 of the exact-f32 tower.  Deviation from the f32
 // forward on the BASELINE networks: policy ≤ 1e-8 absolute / 1e-5 relative, eval ≤ 3e-6 (tests/test_gpu_net.py) —
 // well inside the 1e-4 of BASELINE.json's north_star; plain bf16 (one pass) would miss it by 10×.
-// This is the throughput variant of SURVEY.md §7 step 5; the exact-f32 tower (net_kernels.hip) stays the default.
+// This is the throughput variant of SURVEY.md §7 step 5; the exact-f32 tower (tower_kernels.hip) stays the default.
 //
 // Structure = the f32 towers: a workgroup keeps PW whole positions in LDS for all 1+2R layers, one launch.
 //   k_tower_s3        plain LDS image (batches below 256 positions).  Row of a board square: per chunk of 32 channels eight
@@ -14,7 +14,7 @@
 //                     REGION for off-board taps.  An MFMA B operand (32 k × 16 rows) is two ds_read_b128 per lane (slots q
 //                     and 4 + q of the chunk); ds_read_b128 is served in lane groups that pair 8 rows of one q with 8 rows
 //                     of the next (MI355X_MICROARCH.md §LDS), and this pitch keeps a group on 16 distinct bank quads.
-//   k_tower_s3_halo   the halo image of k_tower_halo (net_kernels.hip): cell pitch F/4 + 1 slots, the same slot table,
+//   k_tower_s3_halo   the halo image of k_tower_halo (tower_kernels.hip): cell pitch F/4 + 1 slots, the same slot table,
 //                     taps as ds_read immediates, pinned half-tile pipeline, weight stream across layers.  Full batches.
 // The A operand (16 output channels × 32 k) is two 16-B loads of the pre-split weights [chunk][tile][hi|lo][q][cout]; a wave
 // owns 2 channel tiles × RTW row tiles (every activation fragment feeds 6 MFMAs) and its 32 output channels are ordered so
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_tower_s3(const voi
     if (CB) {
         const Geom geo = make_geom(n);
         const uint8_t* states = (const uint8_t*)in;
-        // a wave's positions are requested two at a time (tower_stage_states_cb, net_kernels.hip)
+        // a wave's positions are requested two at a time (tower_stage_states_cb, tower_kernels.hip)
         auto stage_one = [&](int p, const WRaw& raw) {
             WState ws;
             ws_unpack(ws, raw, geo);
@@ -447,7 +447,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_tower_s3(const voi
 
 // ------------------------------------------------------------------------------------------------
 // k_tower_s3 on the halo image (full batches): layer 0 on the plain split image with the masked loop, then the
-// F-channel image in halo cells — see k_tower_halo (net_kernels.hip) for the layout, the slot table and why.
+// F-channel image in halo cells — see k_tower_halo (tower_kernels.hip) for the layout, the slot table and why.
 // Same products in the same order as k_tower_s3 → identical bits.
 // ------------------------------------------------------------------------------------------------
 template <int RTW, int KC0, int KC, int NB, bool FROM_STATES, bool OUT_SPLIT, int NW, bool CB = false>
@@ -475,7 +475,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_tower_s3_halo(cons
     if (CB) {
         const Geom geo = make_geom(n);
         const uint8_t* states = (const uint8_t*)in;
-        // a wave's positions are requested two at a time (tower_stage_states_cb, net_kernels.hip)
+        // a wave's positions are requested two at a time (tower_stage_states_cb, tower_kernels.hip)
         auto stage_one = [&](int p, const WRaw& raw) {
             WState ws;
             ws_unpack(ws, raw, geo);
@@ -861,7 +861,7 @@ __global__ __launch_bounds__(NW * 64) void k_fc_s3b(const u32x4* __restrict__ A,
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// k_fc_s3_ring (round 4) — the policy FC on split operands with k_fc_ring's structure (net_kernels.hip): 128 rows × (12 main + 1
+// k_fc_s3_ring (round 4) — the policy FC on split operands with k_fc_ring's structure (fc_kernels.hip): 128 rows × (12 main + 1
 // leftover) output tiles per workgroup, 32 × 8 workgroups, the 99 tiles and the statistics geometry of softmax.cuh, the weights
 // of a K-step of 64 (2 chunks of 32 × 13 tile slots × hi | lo = 52 blocks of 1 KB) through a three-buffer LDS-DMA ring with flag
 // counters, statistics + value pre-activation + logits rows or the children's logits from the epilogue.  What differs:
@@ -900,7 +900,7 @@ __global__ __launch_bounds__(FSR_NW * 64) void k_fc_s3_ring(const u32x4* __restr
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int r16 = lane & 15, q = lane >> 4;
-    // (row block, column block) by XCD as in k_fc_ring (net_kernels.hip): an XCD computes 4 column blocks × every fourth row block, so its
+    // (row block, column block) by XCD as in k_fc_ring (fc_kernels.hip): an XCD computes 4 column blocks × every fourth row block, so its
     // L2 fetches half of the weights and a quarter of the rows twice instead of all the weights and a quarter of the rows once
     int rbx = (int)blockIdx.x, cbx = (int)blockIdx.y;
     if ((gridDim.x & 7) == 0) {

@@ -1,4 +1,4 @@
-// tower_stage.cuh — what the fused towers share around their main loops: the exact-f32 towers (net_kernels.hip: k_tower, k_tower_halo,
+// tower_stage.cuh — what the fused towers share around their main loops: the exact-f32 towers (tower_kernels.hip: k_tower, k_tower_halo,
 // k_tower_sq, k_tower_split) and the split-bf16 towers (net_s3_kernels.hip: k_tower_s3, k_tower_s3_halo) differ in their LDS image and
 // their main loop.  Here: the constant planes of game_repr as a per-position bias of layer 0 (TowerParams.cb / TowerS3Params.cb), and
 // the ReLU on a quad of every epilogue.

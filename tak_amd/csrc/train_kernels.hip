@@ -3,7 +3,7 @@
 // gradients, the weight-gradient (TN) implicit GEMM on f32 MFMA, Adam, and the re-layout of the master
 // parameters (tch layouts) into the fragment layouts of the forward / data-gradient kernels.
 //
-// The forward convolutions and the data gradients reuse k_conv3x3 / k_conv_pos / k_gemm of net_kernels.hip:
+// The forward convolutions and the data gradients reuse k_conv3x3 / k_conv_pos of conv_kernels.hip and k_gemm of fc_kernels.hip:
 // a data gradient is the same implicit GEMM with the taps flipped and the channel roles swapped, which is
 // only a different packing of the weights (k_pack_conv_bwd).
 #include <hip/hip_runtime.h>

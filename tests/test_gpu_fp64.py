@@ -3,7 +3,7 @@ peaked policies, |v| up to 0.9999, BatchNorm channels with running variance of t
 see a dropped bias or a per-mille mis-scale on make_net's flat policies; these gates can (tests/test_forward_gates.py shows it on the CPU).
 
 Every topology the engine dispatches on, both precisions where the split-bf16 path exists, both entry points (tg_policy_eval on packed
-states, tg_forward_mcts on planes), one batch size per launcher bracket of net_kernels.hip (k_tower_split ≤ 128 / ≤ 64 on 6×6 — the
+states, tg_forward_mcts on planes), one batch size per launcher bracket of tower_kernels.hip, conv_kernels.hip and fc_kernels.hip (k_tower_split ≤ 128 / ≤ 64 on 6×6 — the
 states entry only —, the k_tower brackets ≤ 256 / 512 / 1024 / 2048, k_tower_halo above, k_fc_small ≤ 2048 rows against k_fc_ring,
 k_conv_split against k_conv_pos for the conv head, the k_fc_s3 ring above 512 rows) plus ragged sizes; the priors the search computes
 in its tree backup (softmax.cuh's block statistics) against p64[move_index]; the training forward against the fp64 training-mode forward."""

@@ -1,6 +1,6 @@
 """The training step (tg_train_chunk, tg_train_forward) at the chunk sizes where its launchers change kernels, and at ragged sizes in
 between: tests/test_gpu_train.py's gradient gate — fp64 differentiated under the engine's own ReLU decisions, 2e-5 per tensor, 1e-5 on
-the losses, no allowance for flipped decisions — swept over the brackets of net_kernels.hip / train_kernels.hip.  test_gpu_train.CASES
+the losses, no allowance for flipped decisions — swept over the brackets of conv_kernels.hip / fc_kernels.hip / train_kernels.hip.  test_gpu_train.CASES
 runs that gate at 80 – 192 positions per chunk and at exactly 1024, with one residual block wherever the chunk is full; a chunk is
 8 × examples positions, so an odd example count leaves the last workgroup of every whole-position kernel partly filled.
 
