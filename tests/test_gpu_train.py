@@ -39,6 +39,120 @@ def _examples(orc, n, count, seed):
     return sts, cnt.astype(np.int32), mv, visits, results
 
 
+def _sharp_examples(orc, n, sts, v, seed=0):
+    """Examples as a trained network's self-play leaves them, on the positions `sts` (_examples stays as it is: other tests' numbers
+    depend on it).  Example i takes visit pattern i % 5: (a) all visits on one child, (b) two children at 90 % and 10 %, (c) diffuse
+    1 … 49 with about half of the children at zero, (d) all visits on the LAST legal child, (e) all visits on the child whose move
+    index is largest (the oracle's index: the last outputs of the FC head, the last channels of the conv head).  z comes from `v`, the
+    fp64 reference's value of each un-augmented position: z = sign(v) (a decided game the network has understood — the smallest
+    gradient), z = −sign(v) (the largest), z = 0, a third of the examples each ((i // 5) % 3: every pattern meets every z)."""
+    count = len(sts)
+    mv, cnt = orc.movegen(n, sts)
+    rng = np.random.default_rng(seed)
+    visits = np.zeros((count, 512), np.uint32)
+    for i in range(count):
+        k, kind = int(cnt[i]), i % 5
+        if kind == 0:
+            visits[i, rng.integers(k)] = 40
+        elif kind == 1:
+            a, b = rng.choice(k, 2, replace=False) if k > 1 else (0, 0)
+            visits[i, a] += 45
+            visits[i, b] += 5
+        elif kind == 2:
+            visits[i, :k] = rng.integers(1, 50, k) * (rng.random(k) < 0.5)
+            visits[i, rng.integers(k)] += 1
+        elif kind == 3:
+            visits[i, k - 1] = 40
+        else:
+            visits[i, int(np.argmax(orc.move_index(n, mv[i, :k])))] = 40
+    sign = np.where(np.asarray(v) >= 0, 1.0, -1.0)
+    results = (sign * np.array([1.0, -1.0, 0.0])[(np.arange(count) // 5) % 3]).astype(np.float32)
+    return sts, cnt.astype(np.int32), mv, visits, results
+
+
+def trained_case(orc, n, blocks, filters, head, count, seed=32, value_std=2.5, chunks=2):
+    """A trained-like network and `chunks` chunks of `count` sharp-target examples for it (tests/test_gpu_train_trained.py,
+    tests/test_train_gates_trained.py, scripts/train_config_sweep.py --trained).  The network is torch_ref.make_trained_net calibrated
+    on the first chunk's 8-fold augmented planes, as test_training_forward_against_fp64_at_the_launcher_brackets builds it, so the
+    batch statistics of training mode are the calibrated ones: quiet channels with a batch variance near 3e-5, peaked policies, and
+    with value_std = 2.5 (make_trained_net's default of 1.5 leaves ≈ 8 % of the rows at |v| ≥ 0.99) a saturated value on every fourth
+    row.  The premises are asserted on the fp64 reference of every chunk, and so is
+    torch_ref.SLICE_CONDITION on the accumulated fp64 gradients (seed 32 meets it on every case of test_gpu_train_trained).  → (net, [examples per chunk])"""
+    import posgen
+
+    if seed is None:   # topologies outside the suite (scripts/train_config_sweep.py): the first seed whose fp64 reference meets the premises
+        for seed in range(32, 48):
+            try:
+                return trained_case(orc, n, blocks, filters, head, count, seed=seed, value_std=value_std, chunks=chunks)
+            except AssertionError:
+                continue
+        raise AssertionError("trained_case: no seed from 32 to 47 meets the premises")
+    sts = posgen.distinct_positions(orc, n, chunks * count, seed=31 + seed, max_plies=60)
+    parts = [sts[k * count: (k + 1) * count] for k in range(chunks)]
+
+    def planes_of(part):
+        mv, cnt = orc.movegen(n, part)
+        visits = np.zeros((len(part), 512), np.uint32)
+        visits[:, 0] = 1
+        return _targets(orc, n, head, (part, cnt.astype(np.int32), mv, visits, np.zeros(len(part), np.float32)))[0]
+
+    net = torch_ref.make_trained_net(n, blocks, filters, head, planes_of(parts[0])[:512], seed=seed, value_std=value_std)
+    examples = []
+    for part in parts:
+        planes = planes_of(part)
+        ref = torch_ref.forward64(net, planes, training=True)
+        var = torch_ref.batch_statistics64(net, planes)[-1][1]   # the last conv layer: quiet by make_trained_net's default
+        peak, saturated = float(np.median(np.exp(ref["logp"]).max(axis=1))), float((np.abs(ref["v"]) >= 0.99).mean())
+        assert (var <= 1e-4).sum() >= 2 and peak >= 0.2 and saturated >= 0.10, (np.sort(var)[:3], peak, saturated)
+        examples.append(_sharp_examples(orc, n, part, ref["v"][::8], seed=seed))
+    # the per-element slices are well conditioned (torch_ref.SLICE_CONDITION), by the fp64 reference under its own decisions
+    g64 = None
+    for ex in examples:
+        planes, pi, z, _ = _targets(orc, n, head, ex)
+        (g,), _ = torch_ref.fp64_gradients(net, planes, pi, z, [None])
+        g64 = g if g64 is None else {k: g64[k] + g[k] for k in g}
+    for name, g in g64.items():
+        if torch_ref.slice_class(name).startswith("bn."):
+            assert np.abs(g).min() >= torch_ref.SLICE_CONDITION * np.sqrt((g ** 2).mean()), (name, "an element's gradient nearly cancels: another seed")
+    return net, examples
+
+
+def value_sub_batches(orc, net, n, head, ex, pool=48, centre=6.0, spread=1.5):
+    """Three small chunks in which k_value_train's `1 − v²` stands alone in the value head's gradients: EVERY row saturated.  The 8
+    symmetric copies of an example have nearly independent values, and BatchNorm normalises a sub-batch with its own statistics, so
+    rows cannot be picked from a mixed chunk; instead each sub-batch gets a copy of `net` whose value head is re-centred on the
+    sub-batch (pre-activation ≈ ±centre with a standard deviation of `spread`: v of one sign, |v| from 0.99 to 1 − 1e-8), and the
+    examples with a row below |v| = 0.99 in the fp64 forward OF THE SUB-BATCH are dropped until none is left.  Taken from the first
+    `pool` examples of `ex`:  z = sign(v) on every row (the smallest gradient), z = −sign(v) on every row (the largest), and v < 0
+    with z cycling through sign(v), −sign(v), 0.  → {name: (network, examples)}; the callers assert the
+    premises on the fp64 reference."""
+    import copy
+
+    import torch
+
+    out = {}
+    for name, mu, pattern in (("z = sign(v)", centre, (1.0,)), ("z = -sign(v)", centre, (-1.0,)), ("mixed z, v < 0", -centre, (1.0, -1.0, 0.0))):
+        keep = np.arange(min(pool, len(ex[0])))
+        sub_net = copy.deepcopy(net)
+        for it in range(12):
+            sub = [a[keep] for a in ex]
+            planes = _targets(orc, n, head, sub)[0]
+            if it == 0:
+                pre = torch_ref.forward64(net, planes, training=True)["pre"]
+                k = spread / pre.std()
+                with torch.no_grad():
+                    sub_net.value.bias.fill_(float(mu - k * (pre.mean() - float(net.value.bias))))
+                    sub_net.value.weight.mul_(float(k))
+            v = torch_ref.forward64(sub_net, planes, training=True)["v"].reshape(-1, 8)
+            ok = ((np.abs(v) >= 0.99) & (np.sign(v) == np.sign(mu))).all(axis=1)
+            if ok.all():
+                break
+            keep = keep[ok]
+        sub[4] = np.resize(np.array(pattern, np.float32) * np.float32(np.sign(mu)), len(keep)).astype(np.float32)
+        out[name] = (sub_net, tuple(sub))
+    return out
+
+
 def _targets(orc, n, head, ex):
     """the 8-fold augmented batch exactly as Example::to_tensors builds it (via the CPU oracle)"""
     sts, cnt, mv, visits, results = ex
@@ -92,12 +206,15 @@ def test_forward_training_vs_torch(orc, n, blocks, filters, head, count):
     e.close()
 
 
-def chunk_gradients_against_fp64(orc, n, blocks, filters, head, count):
+def chunk_gradients_against_fp64(orc, n, blocks, filters, head, count, net=None, examples=None, slices=False):
     """The gradient gate of the training step on one topology and chunk size (shared with tests/test_gpu_train_brackets.py and
     scripts/train_config_sweep.py): two accumulated chunks of `count` examples; losses to relative 1e-5; every tensor against
     torch_ref.fp64_gradients under torch_ref.engine_relu_decisions to 2e-5; the looser PyTorch-f32 sanity bound; Σ policy.bias
-    gradient = 0 on the FC head.  → (worst tensor, its relative distance to fp64)"""
-    net = torch_ref.make_net(n, blocks, filters, head, seed=10 + n)
+    gradient = 0 on the FC head.  → (worst tensor, its relative distance to fp64)
+    net / examples: another network and the chunks to accumulate (tests/test_gpu_train_trained.py: a trained-like network, sharp
+    targets) in place of make_net and _examples; slices=True adds torch_ref.compare_slices' per-slice gates and returns
+    (worst tensor, its distance, {class: worst slice}) instead."""
+    net = torch_ref.make_net(n, blocks, filters, head, seed=10 + n) if net is None else net
     e = _engine(n, blocks, filters, head)
     e.load_state_dict(torch_ref.abi_tensors(net))
     e.train_create(chunk_size=count, chunks_in_step=1000)
@@ -113,7 +230,7 @@ def chunk_gradients_against_fp64(orc, n, blocks, filters, head, count):
     L, positions = 1 + 2 * blocks, count * 8
     g64 = None
     for rep in range(2):  # gradients accumulate over chunks (network.rs:89-96)
-        ex = _examples(orc, n, count, seed=20 + rep)
+        ex = _examples(orc, n, count, seed=20 + rep) if examples is None else examples[rep]
         planes, pi, z, _ = _targets(orc, n, head, ex)
         lp_ref, lz_ref = torch_ref.train_chunk(net, planes, pi, z)
         lp, lz, stepped = e.train_chunk(*ex)
@@ -142,6 +259,12 @@ def chunk_gradients_against_fp64(orc, n, blocks, filters, head, count):
     if head == "fc5":
         gb = e.train_get_grad("policy.bias", shapes["policy.bias"])
         assert abs(float(gb.astype(np.float64).sum())) <= 1e-5
+    if slices:
+        what = f"{n}x{n} {blocks}x{filters} {head} {count} examples"
+        got = {name: e.train_get_grad(name, shapes[name]) for name in ref}
+        by_class, _ = torch_ref.compare_slices(got, g64, head, n, gates=torch_ref.slice_gate, what=what)
+        e.close()
+        return worst + (by_class,)
     e.close()
     return worst
 

@@ -141,7 +141,7 @@ def named_grads(net):
     return {abi_name(k): v.grad.detach().numpy().copy() for k, v in net.named_parameters()}
 
 
-def fp64_gradients(net, planes, pi, z, mask_sets, verbose=False, hook=None):
+def fp64_gradients(net, planes, pi, z, mask_sets, verbose=False, hook=None, dtype=torch.float64, keep_layers=None):
     """fp64 forward of train_inner's loss (network.rs:58-91) on a copy of `net`, then one backward pass per entry of mask_sets:
     None = the fp64 network's own ReLU decisions, a float t = the decisions taken at y > t, a list of 1 + 2·blocks bool tensors
     [B, F, n, n] = THOSE decisions (layer order conv0, res0.conv1, res0.conv2, …).  The backward pass of a ReLU network is the exact
@@ -149,8 +149,13 @@ def fp64_gradients(net, planes, pi, z, mask_sets, verbose=False, hook=None):
     implementation's own decisions on the reference side its gradients have to agree to rounding, with no allowance for "flips".
     hook (tests/test_train_gates.py: how a deliberately wrong operation is put on the reference side) may replace operations of the
     fp64 network: {"conv": f(layer, module, x) → z, "bn": f(layer, module, z) → BatchNorm output, "policy": f(module, x) → logits}
-    with layer = 0 for conv0 / bn0, 1 + 2·i and 2 + 2·i for block i; an absent entry is the module itself.
-    → ([{ABI name: gradient}], [pre-activation of every ReLU, float64 tensors])"""
+    with layer = 0 for conv0 / bn0, 1 + 2·i and 2 + 2·i for block i; an absent entry is the module itself.  Two more entries replace the
+    losses' sums (tests/test_train_gates_trained.py): "policy_loss": f(logits, π) → −Σ π·log_softmax(logits), "value_loss": f(pre, z) →
+    Σ (z − tanh(pre))², both before the division by the batch size.
+    dtype = torch.float32 runs the same graph in PyTorch f32 under the same decisions: the yardstick a per-slice gate is derived from.
+    keep_layers: conv layers whose output z and input x keep their gradients; every result dict then also holds "dz/<layer>" and
+    "dx/<layer>" as [rows][channels] arrays in tg_train_debug_read's NHWC order (dx of conv1 of a block includes the skip path's gradient).
+    → ([{ABI name: gradient}], [pre-activation of every ReLU, tensors of `dtype`])"""
     import copy
 
     class Relu(torch.autograd.Function):
@@ -172,18 +177,28 @@ def fp64_gradients(net, planes, pi, z, mask_sets, verbose=False, hook=None):
                 return g * (x > m), None
             return g * m[ctx.layer], None
 
-    n64 = copy.deepcopy(net).double().train()
+    n64 = copy.deepcopy(net).to(dtype).train()
     for p in n64.parameters():
         p.grad = None
-    x = torch.from_numpy(np.ascontiguousarray(planes, np.float64))
-    pres = []
+    keep_layers = sorted(keep_layers or [])
+    x = torch.from_numpy(np.ascontiguousarray(planes, np.float64)).to(dtype)
+    if 0 in keep_layers:
+        x.requires_grad_(True)
+    pres, kept = [], {}
 
     def relu(t):
         pres.append(t.detach())
         return Relu.apply(t, len(pres) - 1)
 
     hook = hook or {}
-    conv = hook.get("conv", lambda layer, m, t: m(t))
+    conv_op = hook.get("conv", lambda layer, m, t: m(t))
+
+    def conv(layer, m, t):
+        out = conv_op(layer, m, t)
+        if layer in keep_layers:
+            kept[layer] = (out, t)
+        return out
+
     bn = hook.get("bn", lambda layer, m, t: m(t))
     policy = hook.get("policy", lambda m, t: m(t))
     s = relu(bn(0, n64.bn0, conv(0, n64.conv0, x)))
@@ -192,16 +207,21 @@ def fp64_gradients(net, planes, pi, z, mask_sets, verbose=False, hook=None):
         s = relu(bn(2 * i + 2, blk.bn2, conv(2 * i + 2, blk.conv2, y)) + s)
     flat = s.reshape(s.shape[0], -1)
     logits = policy(n64.policy, flat) if n64.head == "fc5" else policy(n64.policy, s).reshape(s.shape[0], -1)
-    logp = torch.log_softmax(logits, dim=1)
-    v = torch.tanh(n64.value(flat))
+    policy_loss = hook.get("policy_loss", lambda lg, t: -(t * torch.log_softmax(lg, dim=1)).sum())
+    value_loss = hook.get("value_loss", lambda pre, t: (t - torch.tanh(pre)).square().sum())
     b = x.shape[0]
-    loss = -(torch.from_numpy(np.ascontiguousarray(pi, np.float64)) * logp).sum() / b + (torch.from_numpy(np.asarray(z, np.float64))[:, None] - v).square().sum() / b
+    pi_t = torch.from_numpy(np.ascontiguousarray(pi, np.float64)).to(dtype)
+    z_t = torch.from_numpy(np.asarray(z, np.float64)).to(dtype)[:, None]
+    loss = policy_loss(logits, pi_t) / b + value_loss(n64.value(flat), z_t) / b
     params = list(n64.named_parameters())
+    extra = [(f"{what}/{l}", kept[l][i]) for l in keep_layers for i, what in enumerate(("dz", "dx"))]
     out = []
     for i, m in enumerate(mask_sets):
         Relu.mode = m
-        gs = torch.autograd.grad(loss, [p for _, p in params], retain_graph=i + 1 < len(mask_sets))
+        gs = torch.autograd.grad(loss, [p for _, p in params] + [t for _, t in extra], retain_graph=i + 1 < len(mask_sets))
         out.append({abi_name(k): g.numpy().copy() for (k, _), g in zip(params, gs)})
+        for (k, _), g in zip(extra, gs[len(params):]):
+            out[-1][k] = g.permute(0, 2, 3, 1).reshape(-1, g.shape[1]).numpy().copy()
         if verbose:
             print(f"  fp64 backward pass {i + 1} of {len(mask_sets)} done", flush=True)
     return out, pres
@@ -269,6 +289,22 @@ def forward64(net, planes, training=False, chunk=512):
     logits = torch.cat([p[0] for p in parts])
     pre = torch.cat([p[1] for p in parts])
     return dict(logits=logits.numpy(), logp=torch.log_softmax(logits, dim=1).numpy(), pre=pre.numpy(), v=torch.tanh(pre).numpy())
+
+
+@torch.no_grad()
+def batch_statistics64(net, planes):
+    """the batch mean and (biased) variance every BatchNorm of `net` normalises `planes` with in training mode, in float64:
+    [(mean, var)] in layer order conv0, res0.conv1, res0.conv2, …"""
+    import copy
+
+    n64 = copy.deepcopy(net).double().train()
+    bns = [n64.bn0] + [b for blk in n64.res for b in (blk.bn1, blk.bn2)]
+    for m in bns:
+        m.momentum = 1.0
+    x = torch.from_numpy(np.ascontiguousarray(planes, np.float64))
+    n64.forward_training(x)
+    rows = x.shape[0] * x.shape[2] * x.shape[3]
+    return [(m.running_mean.numpy().copy(), m.running_var.numpy() * (rows - 1) / rows) for m in bns]
 
 
 def slice_ref(ref, sel):
@@ -400,3 +436,98 @@ def make_trained_net(n, res_blocks, filters, head, planes, seed=0, logit_std=3.0
     net.value.weight *= kv
     net.value.bias.copy_(0.2 - kv * (pre.mean() - net.value.bias))  # centred: the pre-activation spans about ±4
     return net.eval()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Per-slice gates of the training step's gradients (tests/test_gpu_train_trained.py, tests/test_train_gates_trained.py).  A relative
+# norm over a whole tensor hides an error confined to one output channel, and on a trained-like network (make_trained_net: quiet
+# channels) the channels of one tensor differ in scale by two orders of magnitude.  So every tensor is also compared slice by slice —
+# conv weights per output channel, BatchNorm weights and biases per element, the FC policy head per group of 64 outputs (the conv head per
+# output channel), value.weight per input channel — each slice relative to ITS OWN fp64 norm.  A slice whose fp64 norm is below
+# SLICE_FLOOR × the tensor's RMS slice norm is compared absolutely against that floor and counts as left out (at most SLICE_FLOORED_CAP
+# of a tensor's slices).
+# The tolerances are not chosen: TRAIN_SLICE_F32 is the worst per-slice distance of PyTorch FLOAT32 autograd to fp64 under the same ReLU
+# decisions (fp64_gradients(dtype=torch.float32)), per tensor class, over the cases of tests/test_gpu_train_trained.py, two accumulated
+# chunks each, measured on the CPU (python tests/test_train_gates_trained.py prints the table); the gate of a class is
+# max(2e-5, 3 × that) — 3 for another, equally valid summation order, the margin of GATES above.
+# ---------------------------------------------------------------------------------------------------------------------------------
+SLICE_FLOOR = 1e-6
+SLICE_FLOORED_CAP = 0.02
+# A slice of ONE element (a BatchNorm weight's or bias's gradient) is a sum over all rows that can cancel to any degree, and its fp64
+# value moves by up to 1e-4 of the tensor's RMS element between equally valid sets of ReLU decisions (8e-5 between PyTorch f32's and
+# fp64's own decisions on one element of the 33-example 5×5 case).  An element closer to zero than SLICE_CONDITION × RMS has a relative
+# error that is a property of the decision set, not of the arithmetic (PyTorch f32's own error on such an element: 5e-3 under one set,
+# 0.34 under the other, at the same absolute error), and no f32-derived gate means anything there.  test_gpu_train.trained_case asserts,
+# on the fp64 reference alone, that its seed leaves no such element.
+SLICE_CONDITION = 1e-3
+TENSOR_GATE = 2e-5
+TRAIN_SLICE_F32 = {
+    "conv.weight": 2.25e-6, "bn.weight": 1.80e-4, "bn.bias": 9.90e-4, "policy.weight": 6.14e-6, "policy.bias": 9.25e-5,
+    "value.weight": 3.45e-6, "value.bias": 3.77e-6, "dz": 1.49e-6, "dx": 1.07e-5,
+    # test_gpu_train.value_sub_batches: every row at |v| ≥ 0.99, where PyTorch's own 1 − v² loses its digits too
+    "value.weight.saturated": 1.42e-5, "value.bias.saturated": 1.71e-6,
+}
+
+
+def slice_gate(cls):
+    return max(TENSOR_GATE, 3.0 * TRAIN_SLICE_F32[cls])
+
+
+def bias_before_bn(name):
+    """a conv bias in front of a BatchNorm: true gradient exactly zero, outside every relative gate"""
+    return name.endswith(".bias") and "conv" in name and not name.startswith("policy")
+
+
+def slice_class(name):
+    if name.startswith(("policy.", "value.", "dz", "dx")):
+        return name.split("/")[0]
+    if "bn" in name.split(".")[-2]:
+        return "bn." + name.split(".")[-1]
+    return "conv." + name.split(".")[-1]
+
+
+def slice_view(name, a, head, n):
+    """gradient tensor → float64 [slices, elements per slice] (module comment above)"""
+    a = np.asarray(a, np.float64)
+    if name.startswith(("dz", "dx")):
+        return a.T if name.startswith("dz") else a.reshape(-1, n * n * a.shape[1])   # dz per channel, dx per position
+    if name == "value.weight":
+        return a.reshape(-1, n * n)
+    if name.startswith("policy.") and head == "fc5":
+        rows = a.reshape(a.shape[0], -1)
+        pad = -rows.shape[0] % 64
+        return np.concatenate([rows, np.zeros((pad, rows.shape[1]))]).reshape(-1, 64 * rows.shape[1])
+    if a.ndim == 4 or name.startswith("policy."):
+        return a.reshape(a.shape[0], -1)
+    return a.reshape(-1, 1)
+
+
+def slice_distances(name, g, ref, head, n):
+    """→ (per-slice ‖g − ref‖ / max(‖ref‖, floor), which slices are floored)"""
+    G, R = slice_view(name, g, head, n), slice_view(name, ref, head, n)
+    nr = np.linalg.norm(R, axis=1)
+    floor = SLICE_FLOOR * np.sqrt((nr ** 2).mean())
+    return np.linalg.norm(G - R, axis=1) / np.maximum(nr, floor), nr < floor
+
+
+def compare_slices(grads, ref, head, n, gates=None, what="", classes=None):
+    """Every gated tensor of `grads` against `ref` ({ABI name: array}, the conv biases in front of a BatchNorm left out): whole-tensor
+    relative norm and the per-slice distances.  gates = None measures only; gates = slice_gate asserts tensor ≤ TENSOR_GATE, every
+    slice ≤ gates(class) (of `classes` only, where given) and the cap on floored slices.  → {class: (worst slice distance, tensor, slice)}, (worst tensor, its distance)"""
+    worst_slice, worst_tensor = {}, ("", 0.0)
+    for name in ref:
+        if bias_before_bn(name):
+            continue
+        r64 = np.asarray(ref[name], np.float64)
+        whole = float(np.linalg.norm(np.asarray(grads[name], np.float64) - r64) / np.linalg.norm(r64))
+        d, floored = slice_distances(name, grads[name], ref[name], head, n)
+        cls, i = slice_class(name), int(np.argmax(d))
+        if float(d[i]) >= worst_slice.get(cls, (-1.0,))[0]:
+            worst_slice[cls] = (float(d[i]), name, i)
+        if not name.startswith(("dz", "dx")):
+            worst_tensor = max(worst_tensor, (name, whole), key=lambda t: t[1])
+        if gates is not None:
+            assert floored.mean() <= SLICE_FLOORED_CAP, (what, name, "floored slices", int(floored.sum()), len(floored))
+            assert name.startswith(("dz", "dx")) or whole <= TENSOR_GATE, (what, name, "whole tensor against fp64", whole)
+            assert (classes is not None and cls not in classes) or d[i] <= gates(cls), (what, name, f"slice {i} against fp64, relative to its own norm", float(d[i]), gates(cls))
+    return worst_slice, worst_tensor
