@@ -311,7 +311,8 @@ typedef struct TgSearchConfig {
                                  reproducible games (rank r of a sharded run passes r * games)        */
     uint32_t batch;           /* virtual rollouts per tree and iteration before the one network call — the batching of
                                  `Player` (player.rs:77-93; pit.rs BATCH_SIZE 16).  0 = 1 (self_play_parallel: one leaf per game).
-                                 games × batch ≤ TgConfig.max_batch */
+                                 games × batch ≤ TgConfig.max_batch.  IGNORED by tg_selfplay_create, whatever it holds: the
+                                 self-play driver takes its batch from TgSelfPlayConfig.batch */
     int32_t visit_limit;      /* entries of the exploration-rate table = largest visits + virtual visits of one node;
                                  0 = TG_LIMIT_VISITS (16 MB).  Smaller values serve tests of the limit handling */
     int32_t reserved;
@@ -397,7 +398,11 @@ typedef struct TgSelfPlayConfig {
     int32_t max_examples;    /* capacity of the device example ring drained by tg_selfplay_drain */
     int32_t max_game_plies;  /* a game is retired (see TG_LIMIT_*) when it would stage more examples than this;
                                 0 = TG_LIMIT_GAME_PLIES, the size of the per-game staging area (the largest value allowed) */
-    int32_t reserved;
+    int32_t batch;           /* virtual rollouts per game and iteration (Player's batching, player.rs:77-110; the reference's
+                                self_play uses BATCH_SIZE 32, train/src/self_play.rs:11): every iteration hands the network
+                                games × batch leaves.  0 = 1 (this field was `reserved`: a zeroed one behaves as before).
+                                0 ≤ batch ≤ 4096, and games × batch ≤ TgConfig.max_batch with the resnet evaluator, else
+                                TG_ERR_INVALID_ARG */
 } TgSelfPlayConfig;
 
 /* One training example, fixed-size record (reference alpha-tak/src/example.rs:29-33):
@@ -412,7 +417,19 @@ typedef struct TgExampleHeader {
 
 TG_API int tg_selfplay_create(TgEngine* e, const TgSearchConfig* scfg, const TgSelfPlayConfig* cfg);
 /* run `plies` lock-step plies of self_play_parallel's outer loop (opening → instant-win scan
- * → noise → rollouts → pick/play/recycle).  Asynchronous; tg_sync() to wait. */
+ * → noise → rollouts → pick/play/recycle).  Asynchronous; tg_sync() to wait.
+ * One ply at TgSelfPlayConfig.batch = B:
+ *   - opening, instant-win scan, finish and re-root as at B = 1;
+ *   - games under noise_plies run ONE iteration of B virtual rollouts (one network call, B de-virtualisations in rollout
+ *     order) and then receive Dirichlet noise — Player::add_noise, which consumes a batch and then applies the noise;
+ *   - every live game runs `rollouts` iterations of B virtual rollouts, each with one network call of games × B leaves and
+ *     B de-virtualisations in rollout order; between two iterations the de-virtualisations of one and the virtual rollouts
+ *     of the next share one kernel launch;
+ *   - pick, play and recycle as at B = 1.
+ * TgSelfPlayStats.expansions counts rollouts, so it grows B-fold.  A game that runs into a TG_LIMIT_* capacity in the
+ * middle of a batch is retired as at B = 1; the remaining rollouts of that batch are skipped.
+ * Not reproduced: the one batch `Player` keeps in flight across add_noise and play_move (its pipelining), as in tg_pit;
+ * QUAD_ROLLOUT_PLIES (self_play.rs:19,63: four times the rollouts below ply 10). */
 TG_API int tg_selfplay_step(TgEngine* e, int plies);
 /* statistics: finished games, emitted examples, expansions, network evals */
 typedef struct TgSelfPlayStats {

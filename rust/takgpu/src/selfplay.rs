@@ -12,7 +12,8 @@ use crate::{check, net::GpuNet, pack, sys};
 pub struct SelfPlaySettings {
     pub games: i32,         // concurrent games on this GPU (WORKERS = 32 in the reference)
     pub self_play_games: i32, // SELF_PLAY_GAMES
-    pub rollouts: i32,      // ROLLOUTS
+    pub rollouts: i32,      // ROLLOUTS: iterations per move
+    pub batch: i32,         // virtual rollouts per game and iteration (Player's batching, BATCH_SIZE 32 in the reference's self_play); 1 = one leaf per game
     pub noise_alpha: f32,
     pub noise_ratio: f32,
     pub noise_plies: i32,
@@ -30,6 +31,7 @@ impl Default for SelfPlaySettings {
             games: 4096,
             self_play_games: 8192,
             rollouts: 400,
+            batch: 1,
             noise_alpha: 0.2,
             noise_ratio: 0.3,
             noise_plies: 80,
@@ -79,7 +81,7 @@ pub fn self_play_with_report<const N: usize>(network: &GpuNet<N>, s: SelfPlaySet
         exploration_init: 4.0,   // EXPLORATION_INIT, mcts.rs:8
         seed: s.seed,
         slot_base: s.slot_base,
-        batch: 1, // one leaf per game and iteration (self_play.rs:181-210)
+        batch: 0, // ignored by tg_selfplay_create: the driver's batch is TgSelfPlayConfig.batch
         visit_limit: 0, // TG_LIMIT_VISITS
         reserved: 0,
     };
@@ -94,7 +96,7 @@ pub fn self_play_with_report<const N: usize>(network: &GpuNet<N>, s: SelfPlaySet
         total_games: s.self_play_games,
         max_examples: (drain_cap * 4) as i32, // four drain intervals; an overrun is reported below, never waited for
         max_game_plies: 0, // TG_LIMIT_GAME_PLIES: a longer game is retired alone (TgSelfPlayStats.aborted_games)
-        reserved: 0,
+        batch: s.batch, // games × batch ≤ max_batch of the network's engine
     };
     check(unsafe { sys::tg_selfplay_create(network.e, &scfg, &cfg) })?;
     let mut file = s.example_dir.map(|d| File::create(format!("{d}/{}.data", sys_time())).unwrap()); // self_play.rs:98

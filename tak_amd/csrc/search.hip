@@ -97,7 +97,10 @@ static int pool_init(TgEngine* e, Search* s) {
     return TG_OK;
 }
 
-static int search_alloc(TgEngine* e, const TgSearchConfig* cfg) {
+// tree_growth: how many times faster than one leaf per iteration a tree grows under the caller's schedule — the self-play
+// driver runs `rollouts` ITERATIONS per move whatever the batch, so its trees are `batch` times larger; a caller-driven search
+// decides its own iteration count (1).  Only the automatic pool size looks at it.
+static int search_alloc(TgEngine* e, const TgSearchConfig* cfg, size_t tree_growth = 1) {
     if (!e) return fail(TG_ERR_INVALID_ARG, "null engine");
     if (!cfg || cfg->games <= 0 || cfg->games > e->cfg.max_batch) return fail(TG_ERR_INVALID_ARG, "games must be in 1..max_batch");
     const size_t B = cfg->batch ? cfg->batch : 1;  // virtual rollouts per tree and iteration
@@ -128,7 +131,9 @@ static int search_alloc(TgEngine* e, const TgSearchConfig* cfg) {
         TG_HIP(hipMemGetInfo(&free_b, &total_b));
         // (a 32-bit node index addresses 2^32 nodes; the slack chunks added below count against that)
         const size_t index_limit = ((size_t)1 << 32) - (((size_t)3 * cfg->games + 2) << 11);
-        pool_nodes = std::min<size_t>({free_b / 2 / node_bytes, (size_t)cfg->games << 22, index_limit});
+        // (the 2^22 per game are the reference's 10 000 one-leaf rollouts with a factor 4 to spare; `tree_growth` leaves per
+        // iteration keep that factor as long as memory and the index allow)
+        pool_nodes = std::min<size_t>({free_b / 2 / node_bytes, ((size_t)cfg->games << 22) * tree_growth, index_limit});
         pool_nodes = std::max<size_t>(pool_nodes, (size_t)cfg->games << 12);
         s->cfg.arena_nodes = (int32_t)std::min<size_t>(pool_nodes / (size_t)cfg->games, (size_t)1 << 30);
     } else {
@@ -306,16 +311,19 @@ static int search_iterate_many(TgEngine* e, int iters) {
     if (iters <= 0) return TG_OK;
     bind_logits(e);
     GatherScope scope{e};
-    if (s->d.batch == 1 && iters > 1) {
-        // select(0) | net | backup(0)+select(1) | net | … | backup(iters-1): one tree kernel per iteration
+    if (iters > 1) {
+        // select(0) | net | backup(0)+select(1) | net | … | backup(iters-1): one tree kernel per iteration.  With `batch` > 1
+        // every one of them runs all the passes of a game back to back in that game's wave (leaf slot g·batch + pass), and the
+        // network sees games × batch leaves per call
         SearchDev d = s->d;
-        d.pass = 0;
+        d.pass = s->d.batch > 1 ? -1 : 0;
+        const int leaves = s->d.G * s->d.batch;
         launch_select(e->stream, d, nullptr);
         for (int i = 0; i < iters; i++) {
             if (e->cfg.evaluator == TG_EVAL_RESNET) {
                 float* pol = s->d.logits ? nullptr : s->d.policy;
-                int rc = s->d.planes ? net_forward_dev(e, s->d.G, s->d.planes, pol, s->d.eval)
-                                     : net_forward_states_dev(e, s->d.G, s->d.leaf_state, pol, s->d.eval);
+                int rc = s->d.planes ? net_forward_dev(e, leaves, s->d.planes, pol, s->d.eval)
+                                     : net_forward_states_dev(e, leaves, s->d.leaf_state, pol, s->d.eval);
                 if (rc) return rc;
             }
             if (i + 1 < iters) launch_backup_select(e->stream, d);
@@ -629,9 +637,17 @@ int tg_selfplay_create(TgEngine* e, const TgSearchConfig* scfg, const TgSelfPlay
     if (cfg->rollouts < 1 || cfg->max_examples < 1) return fail(TG_ERR_INVALID_ARG, "rollouts and max_examples must be positive");
     if (cfg->max_game_plies < 0 || cfg->max_game_plies > TG_LIMIT_GAME_PLIES)
         return fail(TG_ERR_INVALID_ARG, "max_game_plies must be 0 (= TG_LIMIT_GAME_PLIES) or in 1..TG_LIMIT_GAME_PLIES");
+    // virtual rollouts per game and iteration: TgSelfPlayConfig.batch (0 = 1: self_play_parallel's one leaf per game,
+    // self_play.rs:181-210; > 1: Player's batching as train/src/self_play.rs:21-92 uses it).  TgSearchConfig.batch is ignored.
+    if (cfg->batch < 0) return fail(TG_ERR_INVALID_ARG, "TgSelfPlayConfig.batch must be in 0..4096 (0 = 1)");
+    if (cfg->batch > 4096) return fail(TG_ERR_INVALID_ARG, "TgSelfPlayConfig.batch must be at most 4096 virtual rollouts per game and iteration");
+    const int B = cfg->batch ? cfg->batch : 1;
+    if (e && scfg->games > 0 && e->cfg.evaluator == TG_EVAL_RESNET && (long long)scfg->games * B > (long long)e->cfg.max_batch)
+        return fail(TG_ERR_INVALID_ARG, "games x batch = " + std::to_string((long long)scfg->games * B) +
+                                            " leaves per iteration exceed max_batch = " + std::to_string(e->cfg.max_batch));
     TgSearchConfig sc1 = *scfg;
-    sc1.batch = 1;  // self_play_parallel gathers ONE leaf per game and iteration (self_play.rs:181-210)
-    int rc = search_alloc(e, &sc1);
+    sc1.batch = (uint32_t)B;
+    int rc = search_alloc(e, &sc1, (size_t)B);
     if (rc) return rc;
     Search* s = e->search;
     s->selfplay = true;

@@ -527,6 +527,44 @@ __global__ __launch_bounds__(WPB * 64) void k_backup_select(SearchDev S) {
     TG_TSTAMP(g, 31);
 }
 
+// The same for `batch` > 1 virtual rollouts per tree and iteration (Player's batching, player.rs:77-110): the iteration's
+// de-virtualisations in rollout order, then the next iteration's virtual rollouts, all in the game's wave — what k_backup
+// followed by k_select do in two launches, on the same device functions → same trees.  A kernel of its own, so that the
+// one-leaf k_backup_select keeps its straight-line form.  Between passes the wave's stores are ordered before its later loads
+// by s_waitcnt alone (see k_select).
+// Root hand-over: the root's index, packed position and the alive / abort flags are requested before the first backup (no
+// backup writes them) and consumed by the first select; the root's cold record and its (visits, virtual) come from the LAST
+// backup only — every earlier view of them is stale once a later pass has de-virtualised through the root.  The selects
+// after the first read everything afresh: a pass that retires the game (limit_hit) sets S.abort[g], which the following
+// passes must see to mark their slots skipped (leaf_kind 0: the next backup leaves them alone, and their network rows keep
+// the finite contents of an earlier leaf).
+template <int NB>
+__global__ __launch_bounds__(WPB * 64) void k_backup_select_batch(SearchDev S) {
+    __shared__ uint32_t path_lds[WPB][MAX_DEPTH];
+    __shared__ uint16_t mv_lds[WPB][EX_MOVES];
+    const int g = game_of_wave();
+    if (g >= S.G) return;
+    RootPre pre;
+    const uint32_t root_v = S.root[g];
+    const Geom geo = make_geom(NB ? NB : S.n);
+    pre.raw = ws_load_raw(S.root_state + (size_t)g * geo.bytes, geo);
+    pre.alive_v = (uint32_t)S.alive[g];
+    pre.abort_v = (uint32_t)S.abort[g];
+    pre.on = true;
+    const int B = S.batch;
+    for (int p = 0; p < B; p++) {
+        backup_pass<NB>(S, g, p, root_v, p + 1 == B ? &pre : nullptr);
+        wave_sync_mem();
+    }
+    uint32_t* path = path_lds[threadIdx.x >> 6];
+    uint16_t* mvl = mv_lds[threadIdx.x >> 6];
+    for (int p = 0; p < B; p++) {
+        select_pass<NB>(S, nullptr, g, p, path, mvl, pre);
+        pre.on = false;
+        if (p + 1 < B) wave_sync_mem();
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // apply_dirichlet, noise.rs:6-16
 // ------------------------------------------------------------------------------------------------
@@ -1104,7 +1142,10 @@ static inline dim3 wgrid(int G) { return dim3((G + WPB - 1) / WPB); }
     } while (0)
 void launch_select(hipStream_t st, const SearchDev& S, const uint8_t* active) { TG_BY_BOARD(k_select, S, active); }
 void launch_backup(hipStream_t st, const SearchDev& S) { TG_BY_BOARD(k_backup, S); }
-void launch_backup_select(hipStream_t st, const SearchDev& S) { TG_BY_BOARD(k_backup_select, S); }
+void launch_backup_select(hipStream_t st, const SearchDev& S) {
+    if (S.batch > 1) TG_BY_BOARD(k_backup_select_batch, S);
+    else TG_BY_BOARD(k_backup_select, S);
+}
 void launch_dirichlet(hipStream_t st, const SearchDev& S, const uint8_t* active, float alpha, float ratio) {
     hipLaunchKernelGGL(k_dirichlet, dim3(S.G), dim3(64), 0, st, S, active, alpha, ratio);
 }

@@ -49,7 +49,7 @@ class TgProfile(C.Structure):
 class TgSelfPlayConfig(C.Structure):
     _fields_ = [("rollouts", C.c_int32), ("noise_plies", C.c_int32), ("exploit_plies", C.c_int32),
                 ("noise_alpha", C.c_float), ("noise_ratio", C.c_float), ("komi", C.c_int32),
-                ("total_games", C.c_int32), ("max_examples", C.c_int32), ("max_game_plies", C.c_int32), ("reserved", C.c_int32)]
+                ("total_games", C.c_int32), ("max_examples", C.c_int32), ("max_game_plies", C.c_int32), ("batch", C.c_int32)]
 
 
 class TgSelfPlayStats(C.Structure):
@@ -702,10 +702,12 @@ class Engine:
     # ---- self_play_parallel ------------------------------------------------------------------------
     def selfplay_create(self, games, arena_nodes=0, base=500.0, init=4.0, seed=0, rollouts=400, noise_plies=80,
                         exploit_plies=40, noise_alpha=0.2, noise_ratio=0.3, komi=2, total_games=0, max_examples=1 << 16,
-                        slot_base=0, max_game_plies=0, visit_limit=0):
+                        slot_base=0, max_game_plies=0, visit_limit=0, batch=1):
+        """batch: virtual rollouts per game and iteration (Player's batching; the reference's self_play uses 32): `rollouts`
+        iterations of `batch` rollouts per move, games * batch leaves per network call, games * batch <= max_batch"""
         scfg = TgSearchConfig(games, arena_nodes, base, init, seed, slot_base, 0, visit_limit, 0)
         cfg = TgSelfPlayConfig(rollouts, noise_plies, exploit_plies, noise_alpha, noise_ratio, komi, total_games, max_examples,
-                               max_game_plies, 0)
+                               max_game_plies, batch)
         self._check(self.lib.tg_selfplay_create(self.h, C.byref(scfg), C.byref(cfg)))
         self.games = games
 
