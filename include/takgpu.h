@@ -520,6 +520,33 @@ TG_API int tg_train_debug_read(TgEngine* e, const char* what, int layer, float* 
 /* make the trained parameters the ones tg_policy_eval / search / self-play use (tg_net_set_tensor of every
  * tensor + tg_net_finalize).  With a communicator the BN running statistics are averaged over the ranks first. */
 TG_API int tg_train_commit(TgEngine* e);
+/* Held-out evaluation: the losses of the DEPLOYED network — the folded-BatchNorm inference network that tg_policy_eval, the
+ * search and self-play run, as tg_net_finalize / tg_train_commit last installed it, in tg_net_set_precision's arithmetic — on
+ * examples (layout of tg_selfplay_drain / tg_train_chunk, host).  No counterpart in the reference, which prints the training
+ * losses of network.rs:86 only: those use batch statistics, on the batch just fitted.  Running statistics here, never batch
+ * statistics; no parameter, running statistic or trainer state changes; a search or self-play run on the same engine keeps its
+ * trees, example ring and counters.  The engine must use TG_EVAL_RESNET with finalized weights, else TG_ERR_STATE.
+ *   n ≥ 0 is any size: the call slices by TgConfig.max_batch itself and synchronises; n = 0 gives zero sums.
+ *   Every example is checked on the host before the first launch as by tg_train_chunk (a reachable state, 1 ≤ n_moves ≤
+ *     TG_MAX_MOVES, at least one visit) → TG_ERR_INVALID_ARG naming the example.
+ *   symmetries = 1: the 8 dihedral images of every example in tg_augment_examples' order, position 8i + s; states and moves
+ *     are transformed on the device, no dense policy target is built.
+ *   Both arg-maxes of top1 run over the example's LISTED moves in list order, the first maximum wins.
+ *   rows (optional): positions × 4 floats {loss_p, loss_z, top1 (0 / 1), v}.  A row depends on its own position only, and the
+ *     f64 sums are taken in position order: the same bits for any max_batch.  Adding the sums of several calls keeps the
+ *     integer fields exact and the f64 fields up to the caller's own addition order. */
+typedef struct TgExampleMetrics {   /* SUMS over positions, so ranks and calls can be added */
+    double loss_p;        /* Σ −Σ_m π(m)·log softmax(logits)[move_index(m)],  π = visits/Σvisits   (network.rs:81-84) */
+    double loss_z;        /* Σ (z − v)²,  v = tanh(value head), z = Example::result                 */
+    double target_entropy;/* Σ −Σ_m π(m)·log π(m)  (0·log 0 = 0): loss_p − this = KL(π‖p)           */
+    uint64_t top1;        /* positions where the network's best LEGAL move is the most visited move  */
+    uint64_t sign_ok;     /* positions with z ≠ 0 and v·z > 0                                        */
+    uint64_t decided;     /* positions with z ≠ 0                                                    */
+    uint64_t positions;   /* n, or 8n with symmetries                                                */
+} TgExampleMetrics;
+TG_API int tg_eval_examples(TgEngine* e, int n, const void* states, const int32_t* n_moves, const TgMove* moves,
+                            const uint32_t* visits, const float* results, int symmetries /* 0 or 1 */,
+                            TgExampleMetrics* sums, float* rows /* optional: positions × 4 = loss_p, loss_z, top1, v */);
 /* RCCL communicator for the gradient all-reduce: rank 0 calls tg_comm_unique_id (128 bytes) and hands the id
  * to every rank (any host transport); then every rank calls tg_train_comm_init. */
 TG_API int tg_comm_unique_id(void* id128);

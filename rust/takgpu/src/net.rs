@@ -164,6 +164,22 @@ impl<const N: usize> GpuNet<N> {
         check(unsafe { sys::tg_train_commit(self.e) })?; // policy_eval / self-play / pit now use the trained weights
         Ok((lp, lz, steps))
     }
+
+    /// Losses of the deployed network — folded BatchNorm, running statistics: what `policy_eval`, self-play and the pit run — on
+    /// examples it may never have seen (tg_eval_examples; the reference prints network.rs:86's training losses only).  Returns the
+    /// SUMS over positions (`examples.len()`, or 8 × that with `symmetries`), which add over calls and ranks: means are
+    /// `loss_p / positions`, KL = `(loss_p - target_entropy) / positions`, `top1 / positions`, `sign_ok / decided`.
+    /// Changes no parameter, running statistic or trainer state.
+    pub fn evaluate_examples(&self, examples: &[Example<N>], symmetries: bool) -> Result<sys::TgExampleMetrics, crate::TgError> {
+        let refs: Vec<&Example<N>> = examples.iter().collect();
+        let a = pack::pack_examples::<N>(&refs);
+        let mut sums = sys::TgExampleMetrics { loss_p: 0.0, loss_z: 0.0, target_entropy: 0.0, top1: 0, sign_ok: 0, decided: 0, positions: 0 };
+        check(unsafe {
+            sys::tg_eval_examples(self.e, refs.len() as i32, a.states.as_ptr() as *const _, a.n_moves.as_ptr(), a.moves.as_ptr(),
+                                  a.visits.as_ptr(), a.results.as_ptr(), symmetries as i32, &mut sums, std::ptr::null_mut())
+        })?;
+        Ok(sums)
+    }
 }
 
 impl<const N: usize> Default for GpuNet<N> {

@@ -3,6 +3,11 @@
 Everything runs through the C ABI (no CPU checker involved).  Prints timings of the training step.
 
     python scripts/train_loop.py [--blocks 10 --filters 128 --games 1024 --rollouts 32 --examples 4000]
+
+--holdout FRACTION (default 0: nothing changes) harvests FRACTION x examples more per round, keeps a seeded share of that
+size out of tg_train and prints the deployed network's losses on it (tg_eval_examples: folded BatchNorm, running statistics)
+before training and for the candidate after tg_train_commit, beside the pit line.  Under a launcher (RANK / WORLD_SIZE) every
+rank plays and holds out its own games and the sums are added over the ranks (tak_amd.dist.reduce_example_sums).
 """
 import argparse
 import json
@@ -17,7 +22,18 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def main():
+def holdout_split(n, hold, seed):
+    """(train indices, held-out indices) of a harvest of n examples: `hold` of them, drawn by a permutation seeded with
+    `seed`, are kept out of training; both lists keep the harvest's order.  hold = 0 → (every index, none)."""
+    if hold <= 0:
+        return np.arange(n), np.zeros(0, np.int64)
+    held = np.sort(np.random.default_rng(seed).permutation(n)[:hold])
+    keep = np.ones(n, bool)
+    keep[held] = False
+    return np.flatnonzero(keep), held
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--board", type=int, default=5)
     ap.add_argument("--blocks", type=int, default=10)
@@ -31,11 +47,28 @@ def main():
     ap.add_argument("--pit-pairs", type=int, default=0, help="> 0: gate every round with tg_pit (train/src/main.rs:98-106)")
     ap.add_argument("--pit-rollouts", type=int, default=50, help="batches per move (pit.rs ROLLOUTS)")
     ap.add_argument("--pit-batch", type=int, default=16, help="virtual rollouts per batch (pit.rs BATCH_SIZE)")
-    args = ap.parse_args()
+    ap.add_argument("--holdout", type=float, default=0.0, help="> 0: harvest this fraction of --examples more, keep it out of training and "
+                    "print the network's losses on it before training and after the commit (tg_eval_examples)")
+    ap.add_argument("--holdout-seed", type=int, default=0, help="seed of the held-out share (round r uses [seed, r])")
+    args = ap.parse_args(argv)
+    if not 0.0 <= args.holdout < 1.0:
+        ap.error("--holdout must be in [0, 1)")
+    return args
+
+
+def main():
+    args = parse_args()
 
     import tak_amd
     import torch_ref  # random-init weights in tch layout (PyTorch default init)
+    from tak_amd import dist as tdist
 
+    hold = int(round(args.holdout * args.examples))
+    harvest = args.examples + hold
+    rank, world, group = 0, 1, None
+    if hold:  # the held-out sums of all ranks are added; without --holdout the loop stays the single-process rehearsal it was
+        rank, world, _ = tdist.env_rank()
+        group = tdist.init("gloo", rank, world)
     head = "fc5" if args.board == 5 else "conv"
     net = torch_ref.make_net(args.board, args.blocks, args.filters, head, seed=0, randomize_bn=False)
     eng = tak_amd.Engine(args.board, res_blocks=args.blocks, filters=args.filters, evaluator=tak_amd.EVAL_RESNET, max_batch=args.games)
@@ -47,24 +80,37 @@ def main():
         old = tak_amd.Engine(args.board, res_blocks=args.blocks, filters=args.filters, evaluator=tak_amd.EVAL_RESNET,
                              max_batch=2 * args.pit_pairs * args.pit_batch)
         old.load_state_dict(tensors)
-    eng.selfplay_create(args.games, arena_nodes=1 << 13, seed=0, rollouts=args.rollouts, max_examples=4 * args.examples)
+    eng.selfplay_create(args.games, arena_nodes=1 << 13, seed=0, rollouts=args.rollouts, max_examples=4 * harvest,
+                        slot_base=tdist.slot_base(rank, args.games))
     report = []
     for rnd in range(args.rounds):
         t0 = time.perf_counter()
         got = [np.zeros((0,), tak_amd.engine.EXAMPLE_HEADER), np.zeros((0, eng.sb), np.uint8), np.zeros((0, 512), np.uint16), np.zeros((0, 512), np.uint32)]
-        while len(got[0]) < args.examples:
+        while len(got[0]) < harvest:
             eng.selfplay_step(4)
             eng.sync()
-            part = eng.selfplay_drain(args.examples)
+            part = eng.selfplay_drain(harvest)
             got = [np.concatenate([a, b]) for a, b in zip(got, part)]
         t_sp = time.perf_counter() - t0
-        hdr, states, moves, visits = [a[: args.examples] for a in got]
+        hdr, states, moves, visits = [a[:harvest] for a in got]
+        held_out = None
+        if hold:
+            keep, held = holdout_split(harvest, hold, [args.holdout_seed, rnd])
+            held_ex = (states[held], hdr["n_moves"][held], moves[held], visits[held], hdr["result"][held])
+            hdr, states, moves, visits = hdr[keep], states[keep], moves[keep], visits[keep]
+
+            def held_means():  # the sums of every rank's held-out examples, then the means
+                return tak_amd.engine.example_means(tdist.reduce_example_sums(group, eng.evaluate_examples(*held_ex)["sums"]))
+
+            held_out = {"examples": hold * world, "before": held_means()}
         t0 = time.perf_counter()
         lp, lz, steps = eng.train(states, hdr["n_moves"], moves, visits, hdr["result"], seed=rnd)
         t_tr = time.perf_counter() - t0
         t0 = time.perf_counter()
         eng.train_commit()
         t_commit = time.perf_counter() - t0
+        if held_out is not None:  # the candidate, as the pit is about to play it
+            held_out["after"] = held_means()
         gate = None
         if old is not None:  # training_loop: keep the new network only if it beats the old one (WIN_RATE_THRESHOLD 0.55)
             t0 = time.perf_counter()
@@ -78,11 +124,14 @@ def main():
                 eng.load_state_dict(tensors)
                 eng.train_create(chunk_size=args.chunk, chunks_in_step=args.chunks_in_step)
             gate["accepted"] = gate["win_rate"] > 0.55
-            eng.selfplay_create(args.games, arena_nodes=1 << 13, seed=rnd + 1, rollouts=args.rollouts, max_examples=4 * args.examples)
+            eng.selfplay_create(args.games, arena_nodes=1 << 13, seed=rnd + 1, rollouts=args.rollouts, max_examples=4 * harvest,
+                                slot_base=tdist.slot_base(rank, args.games))
         chunks = args.examples // args.chunk
         report.append({"round": rnd, "selfplay_s": t_sp, "examples": int(len(hdr)), "train_s": t_tr, "chunks": chunks, "steps": steps,
                        "ms_per_chunk": 1e3 * t_tr / max(chunks, 1), "positions_per_s": chunks * args.chunk * 8 / t_tr,
                        "loss_p": lp, "loss_z": lz, "commit_s": t_commit, "pit": gate, "stats": eng.selfplay_stats()})
+        if held_out is not None:
+            report[-1]["holdout"] = held_out
         print(json.dumps(report[-1]), flush=True)
     eng.close()
     if old is not None:

@@ -675,4 +675,21 @@ __device__ inline int move_index_dev(uint32_t mv, int n, bool legacy5, const int
     return channel * n * n + row * n + col;
 }
 
+// Symmetry (tak/src/symm.rs), shared by the augmentation (k_augment) and the example evaluation (k_example_metrics).
+// Squares: rotate (col,row) → (row, n-1-col), mirror col → n-1-col; symmetry i < 4 is
+// rotate^i, i ≥ 4 is mirror then rotate^(i-4).  Directions follow the squares (Up→Right→Down→Left, Left↔Right).
+__device__ inline void sym_apply(int n, int i, int& col, int& row) {
+    if (i >= 4) col = n - 1 - col;
+    for (int k = 0; k < (i & 3); k++) { int c = row, r = n - 1 - col; col = c; row = r; }
+}
+__device__ inline void sym_apply_inverse(int n, int i, int& col, int& row) {
+    for (int k = 0; k < (i & 3); k++) { int c = n - 1 - row, r = col; col = c; row = r; }
+    if (i >= 4) col = n - 1 - col;
+}
+__device__ inline uint32_t sym_dir(int i, uint32_t d) {
+    if (i >= 4) d = d == LEFT ? RIGHT : d == RIGHT ? LEFT : d;
+    for (int k = 0; k < (i & 3); k++) d = d == UP ? RIGHT : d == RIGHT ? DOWN : d == DOWN ? LEFT : UP;
+    return d;
+}
+
 }  // namespace tg

@@ -129,23 +129,8 @@ __global__ __launch_bounds__(256) void k_board_pass(const uint8_t* __restrict__ 
     if (lane_id() == 0) { results[gi] = (uint8_t)r; counts[gi] = c; }
 }
 
-// Symmetry (tak/src/symm.rs) + Example::to_tensors (alpha-tak/src/example.rs:62-78): one wave per
-// (example, symmetry).  Squares: rotate (col,row) → (row, n-1-col), mirror col → n-1-col; symmetry i < 4 is
-// rotate^i, i ≥ 4 is mirror then rotate^(i-4).  Directions follow the squares (Up→Right→Down→Left, Left↔Right).
-__device__ inline void sym_apply(int n, int i, int& col, int& row) {
-    if (i >= 4) col = n - 1 - col;
-    for (int k = 0; k < (i & 3); k++) { int c = row, r = n - 1 - col; col = c; row = r; }
-}
-__device__ inline void sym_apply_inverse(int n, int i, int& col, int& row) {
-    for (int k = 0; k < (i & 3); k++) { int c = n - 1 - row, r = col; col = c; row = r; }
-    if (i >= 4) col = n - 1 - col;
-}
-__device__ inline uint32_t sym_dir(int i, uint32_t d) {
-    if (i >= 4) d = d == LEFT ? RIGHT : d == RIGHT ? LEFT : d;
-    for (int k = 0; k < (i & 3); k++) d = d == UP ? RIGHT : d == RIGHT ? DOWN : d == DOWN ? LEFT : UP;
-    return d;
-}
-
+// Example::to_tensors (alpha-tak/src/example.rs:62-78) over Symmetry (board.cuh sym_apply / sym_dir): one wave per
+// (example, symmetry).
 __global__ __launch_bounds__(256) void k_augment(const uint8_t* __restrict__ states, const int32_t* __restrict__ n_moves,
                                                  const uint16_t* __restrict__ moves, const uint32_t* __restrict__ visits, int count,
                                                  int n, int P, int legacy5, const int16_t* __restrict__ lut5,

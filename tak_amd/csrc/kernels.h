@@ -43,6 +43,17 @@ void launch_perft_count(hipStream_t st, const uint8_t* states, int count, int n,
 void launch_perft_expand(hipStream_t st, const uint8_t* states, int count, int n, const int64_t* offsets, const int32_t* root_of,
                          uint8_t* next_states, int32_t* next_root);
 
+// eval_kernels.hip (tg_eval_examples)
+// the logits of a slice's positions as the forward left them: per position R rows of cs floats with C valid columns (FC head:
+// R = 1, cs = row stride, C = P; conv head: R = N², cs = cout_pad, C = P / N²); eval = the forward's tanh values, or nullptr:
+// tanh of column C of the FC row (the value head riding in the policy FC)
+struct EvalLogits { const float* logits; size_t pos_stride; int R, cs, C; const float* eval; };
+void launch_eval_images(hipStream_t st, const uint8_t* states, int count, int phase, int n, uint8_t* out);
+hipError_t launch_example_metrics(hipStream_t st, const EvalLogits& L, const int4* ex_rec, const uint16_t* moves, const uint32_t* visits,
+                                  int count, int phase, bool symm, int n, bool legacy5, const int16_t* lut5, float* rows, float* entropy);
+hipError_t launch_eval_sum(hipStream_t st, const float* rows, const float* entropy, const int4* ex_rec, int count, int phase, bool symm,
+                           double* acc);
+
 // conv_kernels.hip
 // stats_part / stats_blocks (optional, training forward): when the launch can emit BatchNorm's column sums from its
 // accumulators (the halo kernel, all channels in one workgroup column) it writes *stats_blocks partial rows

@@ -2,6 +2,7 @@
 // re-layout for the MFMA kernels, and the forward schedule (one kernel per conv layer, heads,
 // softmax) on the engine stream.  Replaces Network<N> of reference alpha-tak/src/model/network.rs:26-35
 // and the concrete Net5 / Net6 (model/net5.rs, net6.rs, res_block.rs) without any tch type.
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -62,6 +63,9 @@ struct Net {
     DevBuf s3_fc, s3_fc_b; // policy FC weights (split) and bias padded to s3_np
     int s3_np = 0;         // padded outputs of the split FC
     bool s3_fc_on = false; // FC head on the split path (tower writes split activations)
+    // tg_eval_examples: a slice's examples (states, {offset, n_moves, result} records, packed move / visit lists), its rows and
+    // target entropies, and the call's sums ({Σ loss_p, Σ loss_z, Σ entropy} f64, {top1, sign_ok, decided} u64)
+    DevBuf ev_states, ev_rec, ev_moves, ev_visits, ev_rows, ev_ent, ev_acc;
     // measurement hooks (tg_profile_*)
     int prof_every = 0;
     uint64_t prof_counter = 0;
@@ -854,6 +858,119 @@ int tg_forward_mcts(TgEngine* e, int n, const float* planes, float* policy, floa
         TG_HIP(hipMemcpyAsync(eval + off, e->s_eval.p, (size_t)k * 4, hipMemcpyDeviceToHost, e->stream));
         TG_HIP(hipStreamSynchronize(e->stream));
     }
+    return TG_OK;
+}
+
+// Losses of the deployed network on examples (no counterpart in the reference: network.rs:86 prints the losses of the batch it
+// has just fitted).  Slices of ≤ max_batch positions: upload the slice's examples with their move lists packed, build the
+// dihedral images on the device (symmetries), run the inference forward with FULL logits rows, k_example_metrics, k_eval_sum.
+int tg_eval_examples(TgEngine* e, int n, const void* states, const int32_t* n_moves, const TgMove* moves, const uint32_t* visits,
+                     const float* results, int symmetries, TgExampleMetrics* sums, float* rows) {
+    if (!e) return fail(TG_ERR_INVALID_ARG, "null engine");
+    if (e->cfg.evaluator != TG_EVAL_RESNET || !e->net) return fail(TG_ERR_STATE, "tg_eval_examples: the engine's evaluator is not TG_EVAL_RESNET");
+    if (!net_ready(e)) return fail(TG_ERR_STATE, "network weights not finalized (tg_net_finalize)");
+    if (!sums) return fail(TG_ERR_INVALID_ARG, "tg_eval_examples: sums is null");
+    if (symmetries != 0 && symmetries != 1) return fail(TG_ERR_INVALID_ARG, "tg_eval_examples: symmetries must be 0 or 1");
+    if (n < 0 || (n > 0 && (!states || !n_moves || !moves || !visits || !results))) return fail(TG_ERR_INVALID_ARG, "tg_eval_examples: bad arguments");
+    if (n > INT_MAX / 8) return fail(TG_ERR_INVALID_ARG, "tg_eval_examples: more than 2^28 examples in one call");
+    std::memset(sums, 0, sizeof(*sums));
+    if (n == 0) return TG_OK;
+    const size_t sb = e->g.bytes;
+    const int mb = e->cfg.max_batch, P = e->policy_size, nsq = e->g.nsq;
+    const bool symm = symmetries == 1;
+    const long total = symm ? 8L * n : n;
+    const uint8_t* hs = (const uint8_t*)states;
+    auto first_ex = [&](long p) { return symm ? p >> 3 : p; };
+    // every example is checked before the first launch (the checks of tg_train_chunk: a reachable state, 1 ≤ n_moves ≤
+    // TG_MAX_MOVES, at least one visit; the visit total must also fit the u32 the kernels divide by)
+    for (int i = 0; i < n; i++) {
+        if (int rc = validate_states(e, 1, hs + (size_t)i * sb, "tg_eval_examples"); rc)
+            return fail(rc, "tg_eval_examples: example " + std::to_string(i) + ": " + tg_last_error());
+        if (n_moves[i] <= 0 || n_moves[i] > TG_MAX_MOVES) return fail(TG_ERR_INVALID_ARG, "tg_eval_examples: example " + std::to_string(i) + ": n_moves out of range");
+        uint64_t tv = 0;
+        for (int k = 0; k < n_moves[i]; k++) tv += visits[(size_t)i * TG_MAX_MOVES + k];
+        if (tv == 0) return fail(TG_ERR_INVALID_ARG, "tg_eval_examples: example " + std::to_string(i) + " without visits (the policy target would be 0/0)");
+        if (tv > UINT32_MAX) return fail(TG_ERR_INVALID_ARG, "tg_eval_examples: example " + std::to_string(i) + ": the visits add up to more than 2^32 - 1");
+    }
+    size_t max_entries = 0;  // the longest packed list of a slice
+    for (long p0 = 0; p0 < total; p0 += mb) {
+        const long k = std::min<long>(mb, total - p0);
+        size_t entries = 0;
+        for (long x = first_ex(p0); x <= first_ex(p0 + k - 1); x++) entries += (size_t)n_moves[x];
+        max_entries = std::max(max_entries, entries);
+    }
+    TG_HIP(hipSetDevice(e->cfg.device));
+    Net* net = e->net;
+    hipStream_t st = e->stream;
+    TG_HIP(hipStreamSynchronize(st));  // (a self-play step may still be running: buffers are (re)allocated below)
+    TG_HIP(net->ev_states.ensure((size_t)mb * sb));
+    TG_HIP(net->ev_rec.ensure((size_t)mb * sizeof(int4)));
+    TG_HIP(net->ev_moves.ensure(max_entries * sizeof(uint16_t)));
+    TG_HIP(net->ev_visits.ensure(max_entries * sizeof(uint32_t)));
+    TG_HIP(net->ev_rows.ensure((size_t)mb * 16));
+    TG_HIP(net->ev_ent.ensure((size_t)mb * 4));
+    TG_HIP(net->ev_acc.ensure(48));
+    TG_HIP(e->s_policy.ensure((size_t)mb * P * 4));
+    TG_HIP(e->s_eval.ensure((size_t)mb * 4));
+    TG_HIP(hipMemsetAsync(net->ev_acc.p, 0, 48, st));
+    // FULL logits rows: the search's gather target (armed only inside its own calls) must not take the FC's output
+    net_set_gather(e, nullptr);
+    int ld = 0;
+    const float* fc_logits = net_fc_logits(e, &ld);
+    EvalLogits L;
+    if (fc_logits) L = EvalLogits{fc_logits, (size_t)ld, 1, ld, P, nullptr};  // logits-only forward: v = tanh(logit P), as k_softmax_stats takes it
+    else if (e->cfg.policy_head == TG_HEAD_CONV) {
+        const int cs = net->policy_conv.cout_pad;
+        L = EvalLogits{net->logits.as<float>(), (size_t)nsq * cs, nsq, cs, P / nsq, e->s_eval.as<float>()};
+    } else {
+        const int stride = net->s3 && net->s3_fc_on ? net->s3_np : net->policy_np;
+        L = EvalLogits{net->logits.as<float>(), (size_t)stride, 1, stride, P, e->s_eval.as<float>()};
+    }
+    std::vector<int4> h_rec;
+    std::vector<uint16_t> h_moves;
+    std::vector<uint32_t> h_visits;
+    for (long p0 = 0; p0 < total; p0 += mb) {
+        const int k = (int)std::min<long>(mb, total - p0);
+        const long ex0 = first_ex(p0), ex1 = first_ex(p0 + k - 1);
+        const int kex = (int)(ex1 - ex0 + 1), phase = (int)(symm ? p0 - 8 * ex0 : 0);
+        h_rec.resize(kex);
+        h_moves.clear();
+        h_visits.clear();
+        for (int i = 0; i < kex; i++) {
+            const size_t x = (size_t)(ex0 + i);
+            int32_t zbits;
+            std::memcpy(&zbits, &results[x], 4);
+            h_rec[i] = int4{(int)h_moves.size(), n_moves[x], zbits, 0};
+            h_moves.insert(h_moves.end(), moves + x * TG_MAX_MOVES, moves + x * TG_MAX_MOVES + n_moves[x]);
+            h_visits.insert(h_visits.end(), visits + x * TG_MAX_MOVES, visits + x * TG_MAX_MOVES + n_moves[x]);
+        }
+        uint8_t* d_pos = e->s_states.as<uint8_t>();
+        TG_HIP(hipMemcpyAsync(symm ? net->ev_states.p : (void*)d_pos, hs + (size_t)ex0 * sb, (size_t)kex * sb, hipMemcpyHostToDevice, st));
+        TG_HIP(hipMemcpyAsync(net->ev_rec.p, h_rec.data(), (size_t)kex * sizeof(int4), hipMemcpyHostToDevice, st));
+        TG_HIP(hipMemcpyAsync(net->ev_moves.p, h_moves.data(), h_moves.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        TG_HIP(hipMemcpyAsync(net->ev_visits.p, h_visits.data(), h_visits.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (symm) {
+            launch_eval_images(st, net->ev_states.as<uint8_t>(), k, phase, e->g.n, d_pos);
+            TG_HIP(hipGetLastError());
+        }
+        if (int rc = net_forward_states_dev(e, k, d_pos, fc_logits ? nullptr : e->s_policy.as<float>(), e->s_eval.as<float>()); rc) return rc;
+        TG_HIP(launch_example_metrics(st, L, net->ev_rec.as<int4>(), net->ev_moves.as<uint16_t>(), net->ev_visits.as<uint32_t>(), k, phase, symm,
+                                      e->g.n, e->legacy5, e->lut5.as<int16_t>(), net->ev_rows.as<float>(), net->ev_ent.as<float>()));
+        TG_HIP(launch_eval_sum(st, net->ev_rows.as<float>(), net->ev_ent.as<float>(), net->ev_rec.as<int4>(), k, phase, symm, net->ev_acc.as<double>()));
+        if (rows) TG_HIP(hipMemcpyAsync(rows + (size_t)p0 * 4, net->ev_rows.p, (size_t)k * 16, hipMemcpyDeviceToHost, st));
+        // (the host lists are rebuilt for the next slice: their copies must have left them)
+        TG_HIP(hipStreamSynchronize(st));
+    }
+    if (int rc = net_poll_errors(e); rc) return rc;
+    uint64_t acc[6];
+    TG_HIP(hipMemcpy(acc, net->ev_acc.p, 48, hipMemcpyDeviceToHost));
+    std::memcpy(&sums->loss_p, &acc[0], 8);
+    std::memcpy(&sums->loss_z, &acc[1], 8);
+    std::memcpy(&sums->target_entropy, &acc[2], 8);
+    sums->top1 = acc[3];
+    sums->sign_ok = acc[4];
+    sums->decided = acc[5];
+    sums->positions = (uint64_t)total;
     return TG_OK;
 }
 

@@ -63,6 +63,24 @@ def reduce_min(dist, value, device="cpu"):
     return t.item()
 
 
+EXAMPLE_SUM_FIELDS = ("loss_p", "loss_z", "target_entropy", "top1", "sign_ok", "decided", "positions")
+
+
+def reduce_example_sums(dist, sums, device="cpu"):
+    """TgExampleMetrics' sums (Engine.evaluate_examples()["sums"]) added over the ranks: one f64 SUM all-reduce of the seven
+    fields.  The counts stay exact below 2^53; the three loss sums are those of the ranks in the reduction's own order."""
+    if dist is None:
+        return dict(sums)
+    import torch
+
+    t = torch.tensor([float(sums[k]) for k in EXAMPLE_SUM_FIELDS], dtype=torch.float64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    out = {k: float(v) for k, v in zip(EXAMPLE_SUM_FIELDS, t.tolist())}
+    for k in EXAMPLE_SUM_FIELDS[3:]:
+        out[k] = int(out[k])
+    return out
+
+
 def gather(dist, obj):
     """[obj of rank 0, obj of rank 1, …] on every rank (all_gather_object; a one-element list without a process group)"""
     if dist is None:

@@ -83,6 +83,24 @@ class TgPitResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class TgExampleMetrics(C.Structure):
+    _fields_ = [("loss_p", C.c_double), ("loss_z", C.c_double), ("target_entropy", C.c_double), ("top1", C.c_uint64),
+                ("sign_ok", C.c_uint64), ("decided", C.c_uint64), ("positions", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def example_means(sums):
+    """The means tg_eval_examples' sums stand for (a dict of TgExampleMetrics' fields, possibly added up over calls or ranks):
+    loss_p, loss_z, kl = loss_p - target entropy, top1, value_sign = sign_ok / decided (nan without decided positions)."""
+    n = sums["positions"]
+    nan = float("nan")
+    return {"loss_p": sums["loss_p"] / n if n else nan, "loss_z": sums["loss_z"] / n if n else nan,
+            "kl": (sums["loss_p"] - sums["target_entropy"]) / n if n else nan, "top1": sums["top1"] / n if n else nan,
+            "value_sign": sums["sign_ok"] / sums["decided"] if sums["decided"] else nan}
+
+
 class TgCommInfo(C.Structure):
     _fields_ = [("attached", C.c_int32), ("world_size", C.c_int32), ("rank", C.c_int32), ("nccl_count", C.c_int32),
                 ("nccl_rank", C.c_int32), ("nccl_version", C.c_int32), ("lib_was_mapped", C.c_int32), ("reserved", C.c_int32),
@@ -113,7 +131,7 @@ ABI_SYMBOLS = [
     "tg_search_root", "tg_search_play", "tg_search_states", "tg_search_dump", "tg_search_debug", "tg_search_counters", "tg_search_pool",
     "tg_selfplay_create", "tg_selfplay_step", "tg_selfplay_stats", "tg_selfplay_drain",
     "tg_profile_enable", "tg_profile_read", "tg_board_pass_bench",
-    "tg_augment_examples",
+    "tg_augment_examples", "tg_eval_examples",
     "tg_train_create", "tg_train_chunk", "tg_train", "tg_train_step", "tg_train_forward", "tg_train_get_tensor",
     "tg_train_get_grad", "tg_train_debug_capture", "tg_train_debug_read", "tg_train_commit", "tg_comm_unique_id", "tg_train_comm_init", "tg_train_set_allreduce",
     "tg_train_grad_buffer", "tg_train_comm_stats", "tg_train_comm_info", "tg_train_comm_preflight", "tg_train_order", "tg_pit",
@@ -492,6 +510,23 @@ class Engine:
 
     def train_commit(self):
         self._check(self.lib.tg_train_commit(self.h))
+
+    def evaluate_examples(self, states, n_moves, moves, visits, results, symmetries=False, rows=False):
+        """tg_eval_examples: the losses of the deployed (folded-BatchNorm, running statistics) network on examples it may never
+        have been trained on.  Returns a dict: the means loss_p, loss_z, kl, top1, value_sign (example_means), "sums" (the raw
+        TgExampleMetrics fields, which add over calls and ranks) and, with rows=True, "rows": positions x 4 float32
+        (loss_p, loss_z, top1, v), position 8 i + s with symmetries."""
+        states, k, n_moves, moves, visits, results = self._examples(states, n_moves, moves, visits, results)
+        sums = TgExampleMetrics()
+        out = np.zeros((k * (8 if symmetries else 1), 4), np.float32) if rows else None
+        self._check(self.lib.tg_eval_examples(self.h, k, _p(states), _p(n_moves), _p(moves), _p(visits), _p(results),
+                                              C.c_int(1 if symmetries is True else 0 if symmetries is False else int(symmetries)),
+                                              C.byref(sums), _p(out) if rows else None))
+        res = example_means(sums.as_dict())
+        res["sums"] = sums.as_dict()
+        if rows:
+            res["rows"] = out
+        return res
 
     def train_set_allreduce(self, fn, world):
         """Route the gradient / BatchNorm-statistics reduction through fn(d_ptr, count, stream) -> 0 | error instead of
