@@ -1,7 +1,7 @@
 import sys, os, itertools
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + "/tests")
-import numpy as np, torch_ref, tak_amd
+import numpy as np, posgen, torch_ref, tak_amd
 from oracle import oracle as orc
 bad = 0
 cfgs = [(3,0,32,"conv"),(3,2,64,"conv"),(4,1,64,"conv"),(4,0,128,"conv"),(4,3,96,"conv"),(5,1,96,"fc5"),(5,3,32,"fc5"),(5,1,160,"conv"),(5,0,64,"fc5"),(5,0,64,"conv"),
@@ -12,15 +12,18 @@ for (n, blocks, filters, head) in cfgs:
             continue
         try:
             net = torch_ref.make_net(n, blocks, filters, head, seed=n * 10 + blocks, randomize_bn=True)
-            e = tak_amd.Engine(n, res_blocks=blocks, filters=filters, policy_head=tak_amd.HEAD_FC5 if head == "fc5" else tak_amd.HEAD_CONV, evaluator=tak_amd.EVAL_RESNET, max_batch=300)
+            # the corner set first (tests/posgen.py: every input plane set somewhere — positions from play leave a quarter of them zero), then play
+            corner, _ = posgen.repr_corner_states(orc, n)
+            sts = np.concatenate([corner, orc.random_positions(n, 400, seed=3, max_plies=60 if n >= 5 else 10, half_komi=4)[:300]])
+            e = tak_amd.Engine(n, res_blocks=blocks, filters=filters, policy_head=tak_amd.HEAD_FC5 if head == "fc5" else tak_amd.HEAD_CONV, evaluator=tak_amd.EVAL_RESNET, max_batch=len(sts))
             if prec != "f32": e.set_precision(prec)
             e.load_state_dict(torch_ref.abi_tensors(net))
-            sts = orc.random_positions(n, 400, seed=3, max_plies=60 if n >= 5 else 10, half_komi=4)[:300]
             p, v = e.policy_eval(sts)
-            p_ref, v_ref = torch_ref.forward(net, orc.encode(n, sts[:64]))
-            dp, dv = np.abs(p[:64] - p_ref).max(), np.abs(v[:64] - v_ref).max()
+            m = len(corner) + 64
+            p_ref, v_ref = torch_ref.forward(net, orc.encode(n, sts[:m]))
+            dp, dv = np.abs(p[:m] - p_ref).max(), np.abs(v[:m] - v_ref).max()
             ok = dp <= 1e-4 and dv <= 1e-4
-            for k in (1, 31, 129, 260):
+            for k in (1, 31, 129, 260, len(corner)):
                 pk, vk = e.policy_eval(sts[:k])
                 if not (np.array_equal(pk, p[:k]) and np.array_equal(vk, v[:k])):
                     ok = False; print("  batch", k, "differs")

@@ -6,6 +6,9 @@
   bits, reserves) — the format's invariants, which is what both implementations are specified on.
 * with_header: copies of states with header bytes (reversible_plies, half_komi, …) overwritten.
 * terminal_mix: whole games from oracle.playouts steered towards every ending of Game::result.
+* empty_board / full_board: the positions on which the board planes of game_repr are all zero / dense.
+* repr_corner_states: a few hundred states per board size that between them set EVERY input plane of game_repr, the board planes on
+  every border class (corner, edge, interior) — what positions from random play never do (tests/test_repr_corners.py).
 """
 import numpy as np
 
@@ -143,3 +146,175 @@ def terminal_mix(orc, n, per_style=3000, seed=1):
             parts.append(orc.playouts(n, per_style, seed=seed * 100 + style * 2 + int(avoid), style=style, avoid_roads=avoid,
                                       max_plies=700))
     return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+
+def empty_board(n, to_move, half_komi=4):
+    S, Cc = STONES[n]
+    st = np.zeros(state_bytes(n), np.uint8)
+    h = st[-16:]
+    h[0] = n
+    h[H_TO_MOVE] = to_move
+    h[H_PLY] = to_move
+    h[H_WS], h[H_WC], h[H_BS], h[H_BC] = S, Cc, S, Cc
+    h[H_KOMI] = np.uint8(half_komi & 0xFF)
+    return st
+
+
+def full_board(n, to_move, caps=None, shift=0, half_komi=4):
+    """every square holds one piece: colour (sq + shift) & 1, a wall where (sq + shift) % 7 = 3, white's and black's capstone (boards
+    that have one) on the squares `caps` (default n + 1 and 3n + 2); reserves = what is left of the supplies"""
+    S, Cc = STONES[n]
+    slots, nsq = (25 if n <= 5 else 36), n * n
+    caps = ((n + 1, 3 * n + 2) if caps is None else tuple(caps)) if Cc else ()
+    st = np.zeros(state_bytes(n), np.uint8)
+    colours = np.zeros(slots, np.uint64)
+    meta = np.zeros(slots, np.uint8)
+    used = {0: [0, 0], 1: [0, 0]}
+    for sq in range(nsq):
+        c = caps.index(sq) if sq in caps else (sq + shift) & 1
+        top = 2 if sq in caps else 1 if (sq + shift) % 7 == 3 else 0
+        colours[sq] = c
+        meta[sq] = 1 | (top << 6)
+        used[c][1 if top == 2 else 0] += 1
+    assert max(used[0][0], used[1][0]) <= S
+    st[: 8 * slots] = colours.view(np.uint8)
+    st[8 * slots: 9 * slots] = meta
+    h = st[-16:]
+    h[0] = n
+    h[H_TO_MOVE] = to_move
+    h[H_PLY] = 50 + to_move
+    h[H_WS], h[H_WC] = S - used[0][0], Cc - used[0][1]
+    h[H_BS], h[H_BC] = S - used[1][0], Cc - used[1][1]
+    h[H_KOMI] = np.uint8(half_komi & 0xFF)
+    return st
+
+
+def border_class(n):
+    """tower_cb_index's class of every square: 3·(y = 0 ? 0 : y = n − 1 ? 2 : 1) + (x = 0 ? 0 : x = n − 1 ? 2 : 1) — which of the 9
+    taps of a 3×3 convolution stay on the board"""
+    k = np.where(np.arange(n) == 0, 0, np.where(np.arange(n) == n - 1, 2, 1))
+    return (3 * k[:, None] + k[None, :]).reshape(-1)
+
+
+def class_squares(n):
+    """one square of every border class, in class order"""
+    cls = border_class(n)
+    return [int(np.flatnonzero(cls == c)[-1 if c == 4 else 0]) for c in range(9)]
+
+
+def reserves_consistent(states, n):
+    """per state: reserves + pieces on the board = the starting supplies, per colour and piece type"""
+    S, Cc = STONES[n]
+    states = np.asarray(states).reshape(-1, states.shape[-1])
+    slots = 25 if n <= 5 else 36
+    hs = heights(states, n).astype(np.uint64)
+    words = np.ascontiguousarray(states[:, : 8 * slots]).view(np.uint64)[:, : n * n]
+    black = np.zeros(words.shape, np.int64)
+    for k in range(62):
+        black += ((words >> np.uint64(k)) & np.uint64(1)).astype(np.int64)
+    tops = states[:, 8 * slots: 8 * slots + n * n] >> 6
+    top_black = ((words >> (np.maximum(hs, 1) - 1)) & np.uint64(1)).astype(bool) & (hs > 0)
+    caps_b = ((tops == 2) & top_black).sum(axis=1)
+    caps_w = ((tops == 2) & ~top_black & (hs > 0)).sum(axis=1)
+    hs = hs.astype(np.int64)
+    return ((header(states, "black_stones") + black.sum(axis=1) - caps_b == S) & (header(states, "black_caps") + caps_b == Cc) &
+            (header(states, "white_stones") + (hs - black).sum(axis=1) - caps_w == S) & (header(states, "white_caps") + caps_w == Cc))
+
+
+def is_position(states, n):
+    """per state: the rules of the engine's host-side check of packed states (validate_states: board size, to_move, reserves within the
+    supplies, nothing beyond the board, empty squares clean, piece type ≤ 2, heights within the supply, no colour bit above the height)"""
+    S, Cc = STONES[n]
+    states = np.asarray(states).reshape(-1, states.shape[-1])
+    slots, nsq = (25 if n <= 5 else 36), n * n
+    hdr = states[:, -16:]
+    ok = (states.shape[1] == state_bytes(n)) & (hdr[:, 0] == n) & (hdr[:, H_TO_MOVE] <= 1)
+    ok &= (hdr[:, H_WS] <= S) & (hdr[:, H_BS] <= S) & (hdr[:, H_WC] <= Cc) & (hdr[:, H_BC] <= Cc)
+    words = np.ascontiguousarray(states[:, : 8 * slots]).view(np.uint64)
+    meta = states[:, 8 * slots: 9 * slots]
+    hs = (meta & 63).astype(np.uint64)
+    ok &= ~(meta[:, nsq:].any(axis=1) | words[:, nsq:].any(axis=1))
+    ok &= ~(((hs == 0) & ((meta != 0) | (words != 0)))[:, :nsq]).any(axis=1)
+    ok &= ((meta >> 6) <= 2).all(axis=1) & (hs <= min(62, 2 * (S + Cc))).all(axis=1) & ~(words >> hs).any(axis=1)
+    return ok & (hs.sum(axis=1) <= 2 * (S + Cc))
+
+
+def _tall_on_classes(n, per_class, seed, lo):
+    """tall_stack_states with the tall stack moved (by exchanging two squares) onto every border class in turn"""
+    sts = tall_stack_states(n, 9 * per_class, seed, lo=lo)
+    slots, sq_of = (25 if n <= 5 else 36), class_squares(n)
+    for i, st in enumerate(sts):
+        a, b = int(np.argmax(heights(st[None], n)[0])), sq_of[i % 9]
+        words, meta = st[: 8 * slots].view(np.uint64), st[8 * slots: 9 * slots]
+        words[[a, b]] = words[[b, a]]
+        meta[[a, b]] = meta[[b, a]]
+    return sts
+
+
+def _reserve_ladder(n):
+    """consistent positions with k stones in white's reserve and S + 1 − k in black's, k = 1 … S: what is missing lies in two
+    one-colour stacks on a diagonal (no road), under either colour to move"""
+    S, Cc = STONES[n]
+    slots = 25 if n <= 5 else 36
+    out = []
+    for k in range(1, S + 1):
+        for to_move in (0, 1):
+            st = empty_board(n, to_move, half_komi=(k % 5) - 2)
+            words, meta = st[: 8 * slots].view(np.uint64), st[8 * slots: 9 * slots]
+            for sq, colour, height in ((0, 0, S - k), (n + 1, 1, k - 1)):
+                if height:
+                    words[sq] = np.uint64((1 << height) - 1 if colour else 0)
+                    meta[sq] = height
+            h = st[-16:]
+            h[H_PLY] = 40 + to_move
+            h[H_WS], h[H_BS] = k, S + 1 - k
+            out.append(st)
+    return np.stack(out)
+
+
+def _other_to_move(states):
+    return with_header(states, to_move=1 - header(states, "to_move").astype(np.int64), ply=header(states, "ply") ^ 1)
+
+
+def repr_corner_states(orc, n, seed=0):
+    """A few hundred packed states (deterministic) on which every input plane of game_repr is set somewhere and zero somewhere, every
+    0/1 board plane on every border class: tall stacks (every depth of the buried-stone planes, the cap at N + 6 included) on a square
+    of each class under both colours to move; full boards with the capstones on each class; the empty board; a ladder of positions over
+    every reserve count; positions from play; and header sweeps over copies — every own / enemy reserve count 0 … S, caps 0 … C, both
+    to_move, half_komi −6 … 6 (−12 … 12 on one of them).  Every state passes tg_search_reset's host-side check.
+    → (states, indices of the states that are ongoing with reserves consistent with the board: the only ones for the search / trainer)"""
+    S, Cc = STONES[n]
+    tall = np.concatenate([_tall_on_classes(n, 2, seed + 11 * n, lo=n + 7), _tall_on_classes(n, 2, seed + 13 * n, lo=33 if n >= 5 else n + 7)])
+    tall = np.concatenate([tall, _other_to_move(tall)])
+    sq_of = class_squares(n)
+    full = np.stack([full_board(n, tm, caps=(sq_of[v], sq_of[(v + 1) % 9]), shift=v) for v in range(9) for tm in (0, 1)])
+    empty = np.stack([empty_board(n, 0), empty_board(n, 1)])
+    ladder = _reserve_ladder(n)
+    play = distinct_positions(orc, n, 32, seed=seed + 5, max_plies={3: 8, 4: 16, 5: 60, 6: 80}[n])
+    # header sweeps: the reserve counts on a position from play and on a tall stack, the komi on three positions
+    base = np.stack([play[-1], tall[0]])
+    base = np.concatenate([base, _other_to_move(base)])
+    sweeps = [with_header(base, white_stones=v, black_stones=S - v) for v in range(S + 1)]
+    sweeps += [with_header(base, white_caps=a, black_caps=b) for a in range(Cc + 1) for b in range(Cc + 1)]
+    sweeps += [with_header(np.stack([play[0], tall[1], ladder[S]]), half_komi=hk) for hk in range(-6, 7)]
+    sweeps += [with_header(play[1][None], half_komi=hk) for hk in list(range(-12, -6)) + list(range(7, 13))]  # (flat counts differ little on 3×3)
+    sts = np.concatenate([tall, full, empty, ladder, play] + sweeps)
+    sts = sts[np.random.default_rng(seed).permutation(len(sts))]  # every kind among the first 64
+    ok = (orc.result(n, sts) == 0) & reserves_consistent(sts, n)
+    return sts, np.flatnonzero(ok)
+
+
+def covering_subset(planes, count):
+    """indices of `count` rows of `planes` [B, C, n, n] chosen greedily so that every channel that is non-zero anywhere is non-zero in
+    one of them (then filled up in order)"""
+    on = np.abs(planes).reshape(planes.shape[0], planes.shape[1], -1).max(axis=2) > 0
+    need, chosen = on.any(axis=0), []
+    while need.any():
+        gain = (on & need).sum(axis=1)
+        gain[chosen] = -1
+        i = int(np.argmax(gain))
+        chosen.append(i)
+        need &= ~on[i]
+    assert len(chosen) <= count, (len(chosen), count)
+    chosen += [i for i in range(len(planes)) if i not in set(chosen)][: count - len(chosen)]
+    return np.array(chosen)

@@ -59,6 +59,22 @@ def test_forward_against_fp64_on_trained_like_networks(orc, name, n, blocks, fil
         e.close()
 
 
+def root_priors_against_fp64(orc, e, n, sts, ref, precision, what):
+    """one search iteration from the roots `sts` on engine `e`: every root's children are the oracle's legal moves and carry
+    p64[move_index(move)] within check_priors' gates (ref = forward64 of the same rows).  → the measured metrics
+    (shared with tests/test_gpu_repr_corners.py)"""
+    e.search_create(len(sts), arena_nodes=1 << 11)
+    e.search_reset(sts)
+    e.search_run(1)
+    r = e.search_root()
+    c = r["counts"]
+    assert np.array_equal(c, orc.movegen(n, sts)[1])
+    mask = np.arange(r["moves"].shape[1])[None, :] < c[:, None]
+    idx = e.move_index(np.where(mask, r["moves"], 0)).reshape(mask.shape)
+    lp = np.take_along_axis(ref["logp"], idx, axis=1)
+    return torch_ref.check_priors(r["prior"], lp, mask, precision, what)
+
+
 @pytest.mark.parametrize("name,n,blocks,filters,head,precision,games", [
     ("c2", 5, 2, 64, "fc5", "f32", 32),       # k_fc_small + k_fc_stats
     ("c2", 5, 2, 64, "fc5", "f32", 1000),
@@ -76,16 +92,7 @@ def test_search_priors_against_fp64(orc, name, n, blocks, filters, head, precisi
     ref = torch_ref.forward64(net, planes)
     e = _engine(n, blocks, filters, head, games, precision)
     e.load_state_dict(torch_ref.abi_tensors(net))
-    e.search_create(games, arena_nodes=1 << 11)
-    e.search_reset(sts)
-    e.search_run(1)
-    r = e.search_root()
-    c = r["counts"]
-    assert np.array_equal(c, orc.movegen(n, sts)[1])
-    mask = np.arange(r["moves"].shape[1])[None, :] < c[:, None]
-    idx = e.move_index(np.where(mask, r["moves"], 0)).reshape(mask.shape)
-    lp = np.take_along_axis(ref["logp"], idx, axis=1)
-    m = torch_ref.check_priors(r["prior"], lp, mask, precision, f"{name} {precision} priors, {games} games")
+    m = root_priors_against_fp64(orc, e, n, sts, ref, precision, f"{name} {precision} priors, {games} games")
     torch_ref.report(f"{name} {precision} search priors G={games}", m)
     e.close()
 

@@ -15,43 +15,8 @@ N = 5
 PLAIN = 2048  # largest batch of the plain-image bracket
 
 
-def _full_board(to_move):
-    """every square holds one piece (flats, a few walls and both capstones), reserves = what is left of 21 + 1"""
-    st = np.zeros(posgen.state_bytes(N), np.uint8)
-    colours = np.zeros(25, np.uint64)
-    meta = np.zeros(25, np.uint8)
-    used = {0: [0, 0], 1: [0, 0]}
-    for sq in range(25):
-        c = sq & 1
-        top = 2 if sq in (6, 17) else 1 if sq % 7 == 3 else 0  # colour = sq & 1: white's capstone on 6, black's on 17
-        colours[sq] = c
-        meta[sq] = 1 | (top << 6)
-        used[c][1 if top == 2 else 0] += 1
-    st[: 8 * 25] = colours.view(np.uint8)
-    st[8 * 25: 9 * 25] = meta
-    h = st[-16:]
-    h[0] = N
-    h[posgen.H_TO_MOVE] = to_move
-    h[posgen.H_PLY] = 50 + to_move
-    h[posgen.H_WS], h[posgen.H_WC] = 21 - used[0][0], 1 - used[0][1]
-    h[posgen.H_BS], h[posgen.H_BC] = 21 - used[1][0], 1 - used[1][1]
-    h[posgen.H_KOMI] = 4
-    return st
-
-
-def _empty_board(to_move):
-    st = np.zeros(posgen.state_bytes(N), np.uint8)
-    h = st[-16:]
-    h[0] = N
-    h[posgen.H_TO_MOVE] = to_move
-    h[posgen.H_PLY] = to_move
-    h[posgen.H_WS], h[posgen.H_WC], h[posgen.H_BS], h[posgen.H_BC] = 21, 1, 21, 1
-    h[posgen.H_KOMI] = 4
-    return st
-
-
 def _positions(orc, total):
-    special = np.stack([_empty_board(0), _empty_board(1), _full_board(0), _full_board(1)])
+    special = np.stack([posgen.empty_board(N, 0), posgen.empty_board(N, 1), posgen.full_board(N, 0), posgen.full_board(N, 1)])
     tall = posgen.tall_stack_states(N, 60, seed=5)
     play = posgen.distinct_positions(orc, N, total - len(special) - len(tall), seed=31)
     sts = np.concatenate([play, special, tall])
