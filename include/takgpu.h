@@ -428,9 +428,34 @@ TG_API int tg_selfplay_create(TgEngine* e, const TgSearchConfig* scfg, const TgS
  *   - pick, play and recycle as at B = 1.
  * TgSelfPlayStats.expansions counts rollouts, so it grows B-fold.  A game that runs into a TG_LIMIT_* capacity in the
  * middle of a batch is retired as at B = 1; the remaining rollouts of that batch are skipped.
- * Not reproduced: the one batch `Player` keeps in flight across add_noise and play_move (its pipelining), as in tg_pit;
- * QUAD_ROLLOUT_PLIES (self_play.rs:19,63: four times the rollouts below ply 10). */
+ * Not reproduced: the one batch `Player` keeps in flight across add_noise and play_move (its pipelining), as in tg_pit.
+ * With a rollout schedule on (tg_selfplay_set_schedule) the call waits once per ply for that ply's first `rollouts`
+ * iterations — the number of boosted games sizes the launches that follow — and still returns before the ply has ended. */
 TG_API int tg_selfplay_step(TgEngine* e, int plies);
+
+/* Rollout schedule of the self-play driver: QUAD_ROLLOUT_PLIES (train/src/self_play.rs:19,63 — a move gets four times the
+ * rollouts while game.ply < QUAD_ROLLOUT_PLIES).  Game::ply is the `ply` of the packed state's header, so after the two
+ * opening moves the first searched move is ply 2: with boost_plies = 10 the moves at plies 2..9 of every game are boosted.
+ * A boosted game's tree after the ply is, bit for bit, the tree of boost_factor × rollouts plain iterations. */
+typedef struct TgRolloutSchedule {
+    int32_t boost_plies;   /* QUAD_ROLLOUT_PLIES 10: a game whose header ply < boost_plies is "boosted" on this move; 0 = off */
+    int32_t boost_factor;  /* 4: a boosted game runs boost_factor × TgSelfPlayConfig.rollouts iterations; 1 = off           */
+    int32_t reserved[2];   /* must be 0 */
+} TgRolloutSchedule;
+/* Set the schedule (train/src/self_play.rs:19,63; ply rule above).  Valid after tg_selfplay_create and before the first
+ * tg_selfplay_step, else TG_ERR_STATE; tg_selfplay_create clears it.  0 ≤ boost_plies ≤ TG_LIMIT_GAME_PLIES,
+ * 1 ≤ boost_factor ≤ 64, reserved zero, rollouts × boost_factor within int32, else TG_ERR_INVALID_ARG naming the field.
+ * Off (boost_plies = 0 or boost_factor = 1) behaves exactly as an engine that never called this.
+ * Per ply with a schedule on: all games run `rollouts` iterations as without one; then the games that are alive, not retired
+ * and under boost_plies are listed on the device, and the remaining (boost_factor − 1) × rollouts iterations run over that
+ * list alone, the network on (listed games) × batch leaves.  The host reads the list's length to size those launches:
+ * tg_selfplay_step waits once per ply for that ply's first `rollouts` iterations, and still returns before the ply ends. */
+TG_API int tg_selfplay_set_schedule(TgEngine* e, const TgRolloutSchedule* s);
+/* Counters of the schedule (train/src/self_play.rs:19,63; ply rule above) since tg_selfplay_create; synchronises.
+ * boosted_moves: game-plies that received the boosted budget; compact_iterations: iterations that ran on a compacted list
+ * (fewer than all games boosted); compact_leaves: leaves handed to the network in those iterations.  All 0 with the schedule
+ * off.  (The one wait per ply of tg_selfplay_step described above is the schedule's only host synchronisation.) */
+TG_API int tg_selfplay_schedule_stats(TgEngine* e, uint64_t* boosted_moves, uint64_t* compact_iterations, uint64_t* compact_leaves);
 /* statistics: finished games, emitted examples, expansions, network evals */
 typedef struct TgSelfPlayStats {
     uint64_t games_finished;

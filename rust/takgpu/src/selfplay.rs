@@ -14,6 +14,8 @@ pub struct SelfPlaySettings {
     pub self_play_games: i32, // SELF_PLAY_GAMES
     pub rollouts: i32,      // ROLLOUTS: iterations per move
     pub batch: i32,         // virtual rollouts per game and iteration (Player's batching, BATCH_SIZE 32 in the reference's self_play); 1 = one leaf per game
+    pub boost_plies: i32,   // QUAD_ROLLOUT_PLIES (10 in the reference's self_play): moves below this ply get boost_factor × rollouts; 0 = off
+    pub boost_factor: i32,  // 4 in the reference's self_play; 1 = off
     pub noise_alpha: f32,
     pub noise_ratio: f32,
     pub noise_plies: i32,
@@ -32,6 +34,8 @@ impl Default for SelfPlaySettings {
             self_play_games: 8192,
             rollouts: 400,
             batch: 1,
+            boost_plies: 0,
+            boost_factor: 1,
             noise_alpha: 0.2,
             noise_ratio: 0.3,
             noise_plies: 80,
@@ -99,6 +103,11 @@ pub fn self_play_with_report<const N: usize>(network: &GpuNet<N>, s: SelfPlaySet
         batch: s.batch, // games × batch ≤ max_batch of the network's engine
     };
     check(unsafe { sys::tg_selfplay_create(network.e, &scfg, &cfg) })?;
+    if s.boost_plies != 0 && s.boost_factor != 1 {
+        // train/src/self_play.rs:19,63; with it tg_selfplay_step waits once per ply (takgpu.h)
+        let schedule = sys::TgRolloutSchedule { boost_plies: s.boost_plies, boost_factor: s.boost_factor, reserved: [0, 0] };
+        check(unsafe { sys::tg_selfplay_set_schedule(network.e, &schedule) })?;
+    }
     let mut file = s.example_dir.map(|d| File::create(format!("{d}/{}.data", sys_time())).unwrap()); // self_play.rs:98
     let sb = pack::state_bytes(N);
     let mut headers = vec![sys::TgExampleHeader { game_id: 0, n_moves: 0, result: 0.0, reserved: 0 }; drain_cap];

@@ -50,7 +50,16 @@ def parse_args(argv=None):
     ap.add_argument("--holdout", type=float, default=0.0, help="> 0: harvest this fraction of --examples more, keep it out of training and "
                     "print the network's losses on it before training and after the commit (tg_eval_examples)")
     ap.add_argument("--holdout-seed", type=int, default=0, help="seed of the held-out share (round r uses [seed, r])")
+    ap.add_argument("--boost-plies", type=int, default=0, help="> 0: moves below this ply get --boost-factor times the rollouts "
+                    "(QUAD_ROLLOUT_PLIES, train/src/self_play.rs:19,63: 10); 0 = off")
+    ap.add_argument("--boost-factor", type=int, default=1, help="rollout multiple of a boosted move (the reference: 4); 1 = off")
     args = ap.parse_args(argv)
+    if not 0 <= args.boost_plies <= 512:
+        ap.error("--boost-plies must be in 0..512 (TG_LIMIT_GAME_PLIES)")
+    if not 1 <= args.boost_factor <= 64:
+        ap.error("--boost-factor must be in 1..64")
+    if args.rollouts * args.boost_factor > 2**31 - 1:
+        ap.error("--rollouts x --boost-factor must fit an int32")
     if not 0.0 <= args.holdout < 1.0:
         ap.error("--holdout must be in [0, 1)")
     return args
@@ -80,8 +89,9 @@ def main():
         old = tak_amd.Engine(args.board, res_blocks=args.blocks, filters=args.filters, evaluator=tak_amd.EVAL_RESNET,
                              max_batch=2 * args.pit_pairs * args.pit_batch)
         old.load_state_dict(tensors)
+    schedule = dict(boost_plies=args.boost_plies, boost_factor=args.boost_factor)
     eng.selfplay_create(args.games, arena_nodes=1 << 13, seed=0, rollouts=args.rollouts, max_examples=4 * harvest,
-                        slot_base=tdist.slot_base(rank, args.games))
+                        slot_base=tdist.slot_base(rank, args.games), **schedule)
     report = []
     for rnd in range(args.rounds):
         t0 = time.perf_counter()
@@ -125,7 +135,7 @@ def main():
                 eng.train_create(chunk_size=args.chunk, chunks_in_step=args.chunks_in_step)
             gate["accepted"] = gate["win_rate"] > 0.55
             eng.selfplay_create(args.games, arena_nodes=1 << 13, seed=rnd + 1, rollouts=args.rollouts, max_examples=4 * harvest,
-                                slot_base=tdist.slot_base(rank, args.games))
+                                slot_base=tdist.slot_base(rank, args.games), **schedule)
         chunks = args.examples // args.chunk
         report.append({"round": rnd, "selfplay_s": t_sp, "examples": int(len(hdr)), "train_s": t_tr, "chunks": chunks, "steps": steps,
                        "ms_per_chunk": 1e3 * t_tr / max(chunks, 1), "positions_per_s": chunks * args.chunk * 8 / t_tr,

@@ -220,6 +220,10 @@ struct DebugOut;
 void launch_select(hipStream_t st, const SearchDev& S, const uint8_t* active);
 void launch_backup(hipStream_t st, const SearchDev& S);
 void launch_backup_select(hipStream_t st, const SearchDev& S);  // backup of iteration i + select of iteration i+1 (all S.batch passes of each)
+// search_list_kernels.hip: the same three over a compacted list of `count` games (wave w serves list[w], leaf slots w·batch + pass, grid sized from count)
+void launch_select_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count);
+void launch_backup_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count);
+void launch_backup_select_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count);
 void launch_dirichlet(hipStream_t st, const SearchDev& S, const uint8_t* active, float alpha, float ratio);
 void launch_apply_noise(hipStream_t st, const SearchDev& S, const uint8_t* active, const float* noise, float ratio);
 void launch_reroot(hipStream_t st, const SearchDev& S, const int32_t* op);
@@ -233,6 +237,8 @@ void launch_sp_instant_win(hipStream_t st, const SearchDev& S, const SelfPlayDev
 void launch_sp_finish(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, int32_t* op);
 void launch_sp_noise_mask(hipStream_t st, const SearchDev& S, const SelfPlayDev& P);
 void launch_sp_pick(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, int32_t* op);
+// (search_list_kernels.hip) the ascending list of the games owed a ply's boosted iterations, and their count
+void launch_sp_boost_list(hipStream_t st, const SearchDev& S, int boost_plies, int32_t* list, int32_t* count);
 void launch_sp_count_ply(hipStream_t st, const SelfPlayDev& P);
 
 }  // namespace tg

@@ -27,6 +27,14 @@ struct Search {
     DevBuf st_hdr, st_state, st_moves, st_visits, st_count, out_hdr, out_state, out_moves, out_visits, fin, recycle, out_off, chosen,
         mask, stats;
     unsigned long long drained = 0, dropped = 0;
+    // rollout schedule (tg_selfplay_set_schedule): games under boost_plies run boost_factor × rollouts iterations, the extra
+    // ones over a compacted list of those games
+    TgRolloutSchedule sched{};
+    bool stepped = false;           // tg_selfplay_step has run: the schedule is fixed
+    DevBuf boost_list, boost_count; // [G] ascending game indices; their count
+    int32_t* h_boost_count = nullptr;  // pinned: the count sizes the grid and the network batch, so the host has to see it
+    unsigned long long boosted_moves = 0, compact_iterations = 0, compact_leaves = 0;
+    ~Search() { if (h_boost_count) (void)hipHostFree(h_boost_count); }
 };
 
 void search_destroy(Search* s) { delete s; }
@@ -249,7 +257,9 @@ static int search_reset_trees(TgEngine* e) {
 // FC-head networks: the backup reads the network's logits buffer directly (softmax statistics and tanh in the tree kernel,
 // softmax.cuh).  Bound per call: the weights may have been re-finalised (tg_train_commit, another precision) since the
 // search was created.
-static void bind_logits(TgEngine* e) {
+// `leaves`: rows of the forwards that follow (0 = games × batch; a compacted iteration passes count × batch — whether the FC
+// serves the gather depends on the batch, the bits do not)
+static void bind_logits(TgEngine* e, int leaves = 0) {
     Search* s = e->search;
     s->d.logits = nullptr;
     s->d.logit_ld = 0;
@@ -267,7 +277,7 @@ static void bind_logits(TgEngine* e) {
         const float* fs = net_fc_stats(e, &blocks, &stride);
         if (fs) { s->d.fc_stats = fs; s->d.fc_blocks = blocks; s->d.fc_stride = stride; }
         // exact-f32 FC at a batch its ring kernel serves: the FC's epilogue hands the backup the children's logits directly
-        if (fs && !s->d.planes && net_gather_ok(e, s->d.G * s->d.batch)) {
+        if (fs && !s->d.planes && net_gather_ok(e, leaves ? leaves : s->d.G * s->d.batch)) {
             const FcGatherArgs g{s->d.child_pidx, s->d.leaf_rec, s->child_logit.as<float>(), EX_MOVES};
             net_set_gather(e, &g);
             s->d.child_logit = s->child_logit.as<float>();
@@ -336,6 +346,32 @@ static int search_iterate_many(TgEngine* e, int iters) {
         int rc = search_iterate(e, nullptr);
         if (rc) return rc;
     }
+    return TG_OK;
+}
+
+// `iters` iterations over the compacted list of `count` games (0 < count < G), fused like search_iterate_many:
+// select | net | backup+select | … | backup, one tree kernel per iteration, the network on count × batch leaves
+static int search_iterate_list(TgEngine* e, int iters, int count) {
+    Search* s = e->search;
+    if (iters <= 0 || count <= 0) return TG_OK;
+    const int leaves = count * s->d.batch;
+    bind_logits(e, leaves);
+    GatherScope scope{e};
+    SearchDev d = s->d;
+    d.pass = s->d.batch > 1 ? -1 : 0;
+    const int32_t* list = s->boost_list.as<int32_t>();
+    launch_select_list(e->stream, d, list, count);
+    for (int i = 0; i < iters; i++) {
+        if (e->cfg.evaluator == TG_EVAL_RESNET) {
+            float* pol = s->d.logits ? nullptr : s->d.policy;
+            int rc = s->d.planes ? net_forward_dev(e, leaves, s->d.planes, pol, s->d.eval)
+                                 : net_forward_states_dev(e, leaves, s->d.leaf_state, pol, s->d.eval);
+            if (rc) return rc;
+        }
+        if (i + 1 < iters) launch_backup_select_list(e->stream, d, list, count);
+        else launch_backup_list(e->stream, d, list, count);
+    }
+    TG_HIP(hipGetLastError());
     return TG_OK;
 }
 
@@ -674,6 +710,10 @@ int tg_selfplay_create(TgEngine* e, const TgSearchConfig* scfg, const TgSelfPlay
     TG_HIP(hipMemsetAsync(s->st_count.p, 0, G * 4, e->stream));
     TG_HIP(hipMemsetAsync(s->stats.p, 0, ST_COUNT * 8, e->stream));
     TG_HIP(hipMemsetAsync(s->fin.p, 0, G, e->stream));
+    TG_HIP(s->boost_list.ensure(G * 4));
+    TG_HIP(s->boost_count.ensure(4));
+    TG_HIP(hipHostMalloc((void**)&s->h_boost_count, 4, hipHostMallocDefault));
+    *s->h_boost_count = 0;
     SelfPlayDev& p = s->p;
     p.st_hdr = s->st_hdr.as<ExampleRec>(); p.st_state = s->st_state.as<uint8_t>(); p.st_moves = s->st_moves.as<uint16_t>();
     p.st_visits = s->st_visits.as<uint32_t>(); p.st_count = s->st_count.as<int32_t>();
@@ -703,6 +743,37 @@ int tg_selfplay_create(TgEngine* e, const TgSearchConfig* scfg, const TgSelfPlay
     return search_reset_trees(e);
 }
 
+int tg_selfplay_set_schedule(TgEngine* e, const TgRolloutSchedule* sc) {
+    int rc = need_search(e);
+    if (rc) return rc;
+    Search* s = e->search;
+    if (!s->selfplay) return fail(TG_ERR_STATE, "tg_selfplay_set_schedule: tg_selfplay_create has not been called");
+    if (s->stepped) return fail(TG_ERR_STATE, "tg_selfplay_set_schedule: the schedule is fixed once tg_selfplay_step has run");
+    if (!sc) return fail(TG_ERR_INVALID_ARG, "tg_selfplay_set_schedule: null schedule");
+    if (sc->boost_plies < 0 || sc->boost_plies > TG_LIMIT_GAME_PLIES)
+        return fail(TG_ERR_INVALID_ARG, "TgRolloutSchedule.boost_plies must be in 0..TG_LIMIT_GAME_PLIES");
+    if (sc->boost_factor < 1 || sc->boost_factor > 64) return fail(TG_ERR_INVALID_ARG, "TgRolloutSchedule.boost_factor must be in 1..64");
+    if (sc->reserved[0] != 0 || sc->reserved[1] != 0) return fail(TG_ERR_INVALID_ARG, "TgRolloutSchedule.reserved must be 0");
+    if ((long long)s->spcfg.rollouts * sc->boost_factor > 2147483647ll)
+        return fail(TG_ERR_INVALID_ARG, "TgSelfPlayConfig.rollouts x TgRolloutSchedule.boost_factor = " +
+                                            std::to_string((long long)s->spcfg.rollouts * sc->boost_factor) + " does not fit an int32");
+    s->sched = *sc;
+    return TG_OK;
+}
+
+int tg_selfplay_schedule_stats(TgEngine* e, uint64_t* boosted_moves, uint64_t* compact_iterations, uint64_t* compact_leaves) {
+    int rc = need_search(e);
+    if (rc) return rc;
+    Search* s = e->search;
+    if (!s->selfplay) return fail(TG_ERR_STATE, "tg_selfplay_schedule_stats: tg_selfplay_create has not been called");
+    rc = sync_and_check(e);
+    if (rc) return rc;
+    if (boosted_moves) *boosted_moves = s->boosted_moves;
+    if (compact_iterations) *compact_iterations = s->compact_iterations;
+    if (compact_leaves) *compact_leaves = s->compact_leaves;
+    return TG_OK;
+}
+
 int tg_selfplay_step(TgEngine* e, int plies) {
     int rc = need_search(e);
     if (rc) return rc;
@@ -711,6 +782,8 @@ int tg_selfplay_step(TgEngine* e, int plies) {
     hipStream_t st = e->stream;
     const size_t G = (size_t)s->d.G;
     int32_t* op = s->op.as<int32_t>();
+    if (plies > 0) s->stepped = true;
+    const bool boost = s->sched.boost_plies > 0 && s->sched.boost_factor > 1;
     for (int ply = 0; ply < plies; ply++) {
         launch_sp_opening(st, s->d);                                   // (a) :110-116
         launch_sp_instant_win(st, s->d, s->p);                         // (b) :119-171
@@ -723,6 +796,25 @@ int tg_selfplay_step(TgEngine* e, int plies) {
         launch_dirichlet(st, s->d, s->p.mask, s->p.noise_alpha, s->p.noise_ratio);
         rc = search_iterate_many(e, s->p.rollouts);                    // (d) :181-210
         if (rc) return rc;
+        if (boost) {
+            // train/src/self_play.rs:19,63: boost_factor × rollouts while game.ply < boost_plies.  The extra iterations run over
+            // the games that are owed them only; their number sizes the grid and the network batch, hence the one wait per ply
+            launch_sp_boost_list(st, s->d, s->sched.boost_plies, s->boost_list.as<int32_t>(), s->boost_count.as<int32_t>());
+            TG_HIP(hipGetLastError());
+            TG_HIP(hipMemcpyAsync(s->h_boost_count, s->boost_count.p, 4, hipMemcpyDeviceToHost, st));
+            TG_HIP(hipStreamSynchronize(st));
+            const int count = *s->h_boost_count;
+            if (count < 0 || count > s->d.G) return fail(TG_ERR_STATE, "tg_selfplay_step: corrupt boost list");
+            const int extra = (s->sched.boost_factor - 1) * s->p.rollouts;
+            s->boosted_moves += (unsigned long long)count;
+            if (count == s->d.G) rc = search_iterate_many(e, extra);
+            else if (count > 0) {
+                rc = search_iterate_list(e, extra, count);
+                s->compact_iterations += (unsigned long long)extra;
+                s->compact_leaves += (unsigned long long)extra * (unsigned long long)count * (unsigned long long)s->d.batch;
+            }
+            if (rc) return rc;
+        }
         launch_sp_pick(st, s->d, s->p, op);                            // (e) :212-258
         launch_sp_finish(st, s->d, s->p, op);
         launch_reroot(st, s->d, op);

@@ -52,6 +52,10 @@ class TgSelfPlayConfig(C.Structure):
                 ("total_games", C.c_int32), ("max_examples", C.c_int32), ("max_game_plies", C.c_int32), ("batch", C.c_int32)]
 
 
+class TgRolloutSchedule(C.Structure):
+    _fields_ = [("boost_plies", C.c_int32), ("boost_factor", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class TgSelfPlayStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in (
         "games_finished", "examples", "expansions", "evals", "plies", "white_wins", "black_wins", "draws", "instant_wins",
@@ -130,6 +134,7 @@ ABI_SYMBOLS = [
     "tg_search_create", "tg_search_reset", "tg_search_run", "tg_search_apply_dirichlet", "tg_search_apply_noise",
     "tg_search_root", "tg_search_play", "tg_search_states", "tg_search_dump", "tg_search_debug", "tg_search_counters", "tg_search_pool",
     "tg_selfplay_create", "tg_selfplay_step", "tg_selfplay_stats", "tg_selfplay_drain",
+    "tg_selfplay_set_schedule", "tg_selfplay_schedule_stats",
     "tg_profile_enable", "tg_profile_read", "tg_board_pass_bench",
     "tg_augment_examples", "tg_eval_examples",
     "tg_train_create", "tg_train_chunk", "tg_train", "tg_train_step", "tg_train_forward", "tg_train_get_tensor",
@@ -737,14 +742,29 @@ class Engine:
     # ---- self_play_parallel ------------------------------------------------------------------------
     def selfplay_create(self, games, arena_nodes=0, base=500.0, init=4.0, seed=0, rollouts=400, noise_plies=80,
                         exploit_plies=40, noise_alpha=0.2, noise_ratio=0.3, komi=2, total_games=0, max_examples=1 << 16,
-                        slot_base=0, max_game_plies=0, visit_limit=0, batch=1):
+                        slot_base=0, max_game_plies=0, visit_limit=0, batch=1, boost_plies=0, boost_factor=1):
         """batch: virtual rollouts per game and iteration (Player's batching; the reference's self_play uses 32): `rollouts`
-        iterations of `batch` rollouts per move, games * batch leaves per network call, games * batch <= max_batch"""
+        iterations of `batch` rollouts per move, games * batch leaves per network call, games * batch <= max_batch
+        boost_plies, boost_factor: the rollout schedule (QUAD_ROLLOUT_PLIES; the reference's self_play uses 10 and 4): a move
+        of a game whose ply < boost_plies gets boost_factor * rollouts iterations.  0 / 1 = off: the setter is not called"""
         scfg = TgSearchConfig(games, arena_nodes, base, init, seed, slot_base, 0, visit_limit, 0)
         cfg = TgSelfPlayConfig(rollouts, noise_plies, exploit_plies, noise_alpha, noise_ratio, komi, total_games, max_examples,
                                max_game_plies, batch)
         self._check(self.lib.tg_selfplay_create(self.h, C.byref(scfg), C.byref(cfg)))
         self.games = games
+        if boost_plies != 0 and boost_factor != 1:
+            self.selfplay_set_schedule(boost_plies, boost_factor)
+
+    def selfplay_set_schedule(self, boost_plies, boost_factor, reserved=(0, 0)):
+        """tg_selfplay_set_schedule as it is: after selfplay_create, before the first selfplay_step"""
+        s = TgRolloutSchedule(boost_plies, boost_factor, (C.c_int32 * 2)(*reserved))
+        self._check(self.lib.tg_selfplay_set_schedule(self.h, C.byref(s)))
+
+    def selfplay_schedule_stats(self):
+        """{boosted_moves, compact_iterations, compact_leaves} since selfplay_create (synchronises)"""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.tg_selfplay_schedule_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"boosted_moves": a.value, "compact_iterations": b.value, "compact_leaves": c.value}
 
     def selfplay_step(self, plies=1):
         self._check(self.lib.tg_selfplay_step(self.h, plies))
