@@ -50,9 +50,16 @@ struct DevBuf {
     template <class T>
     T* as() const { return (T*)p; }
 };
+// `b` sized for `count` elements of the field it is bound to: the field's declared type is the one statement of the element size
+template <class T>
+hipError_t bind(DevBuf& b, T*& field, size_t count) {
+    hipError_t e = b.ensure(count * sizeof(T));
+    field = b.as<T>();
+    return e;
+}
 
 struct Net;     // net.hip
-struct Search;  // search.hip
+struct Search;  // search_host.h
 struct Trainer; // train.hip
 
 }  // namespace tg

@@ -1,4 +1,4 @@
-// search.cuh — device-resident MCTS data layout shared by search_kernels.hip and search.hip.
+// search.cuh — device-resident MCTS data layout shared by the tree kernels and their host code (search.hip, selfplay.hip).
 //
 // Replaces the heap tree of reference alpha-tak/src/search/node.rs:3-39 (Node { policy,
 // expected_reward, result, visits, virtual_visits, children: Box<[(Move, Node)]> }).

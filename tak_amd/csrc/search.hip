@@ -1,41 +1,15 @@
-// search.hip — host side of the search / self-play entry points of include/takgpu.h: device
-// allocation, the per-iteration schedule (select → network → backup, no host synchronisation inside a
-// call), the per-ply schedule of self_play_parallel, result read-back and the tree dump.
+// search.hip — host side of the search entry points of include/takgpu.h: device allocation, the per-iteration schedule
+// (select → network → backup, no host synchronisation inside a call), result read-back and the tree dump.  The self-play
+// entry points are selfplay.hip's.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 
-#include "engine.h"
-#include "kernels.h"
-#include "search.cuh"
+#include "search_host.h"
 
 namespace tg {
-
-struct Search {
-    TgSearchConfig cfg;
-    SearchDev d;
-    DevBuf hot, cold, root, alloc, chunk_head, chunk_link, chunk_fwd, chunk_used, free_ring, pool_ctl, root_state, alive, generation, path_len, path, leaf_kind, leaf_rec, child_pidx, child_logit, leaf_hash, planes, leaf_state, policy, eval,
-        ctab, err, counters, op, active, noise, abort;
-    DevBuf r_moves, r_visits, r_prior, r_q, r_counts, r_rv, r_rq, s_moves;
-    DevBuf dbg_moves, dbg_visits, dbg_reward, dbg_policy, dbg_counts, dbg_eval, dbg_cmoves, dbg_cvisits, dbg_clen;  // tg_search_debug, one slice
-    // self-play
-    bool selfplay = false;
-    TgSelfPlayConfig spcfg;
-    SelfPlayDev p;
-    DevBuf st_hdr, st_state, st_moves, st_visits, st_count, out_hdr, out_state, out_moves, out_visits, fin, recycle, out_off, chosen,
-        mask, stats;
-    unsigned long long drained = 0, dropped = 0;
-    // rollout schedule (tg_selfplay_set_schedule): games under boost_plies run boost_factor × rollouts iterations, the extra
-    // ones over a compacted list of those games
-    TgRolloutSchedule sched{};
-    bool stepped = false;           // tg_selfplay_step has run: the schedule is fixed
-    DevBuf boost_list, boost_count; // [G] ascending game indices; their count
-    int32_t* h_boost_count = nullptr;  // pinned: the count sizes the grid and the network batch, so the host has to see it
-    unsigned long long boosted_moves = 0, compact_iterations = 0, compact_leaves = 0;
-    ~Search() { if (h_boost_count) (void)hipHostFree(h_boost_count); }
-};
 
 void search_destroy(Search* s) { delete s; }
 
@@ -65,7 +39,7 @@ int search_poll_errors(TgEngine* e) {
     return describe_errors(bits);
 }
 
-static int need_search(TgEngine* e) {
+int need_search(TgEngine* e) {
     if (!e) return fail(TG_ERR_INVALID_ARG, "null engine");
     if (!e->search) return fail(TG_ERR_STATE, "tg_search_create / tg_selfplay_create has not been called");
     TG_HIP(hipSetDevice(e->cfg.device));
@@ -77,7 +51,7 @@ static int upload_mask(TgEngine* e, const uint8_t* active, const uint8_t** d_out
     if (!active) return TG_OK;
     Search* s = e->search;
     TG_HIP(hipMemcpyAsync(s->active.p, active, (size_t)s->d.G, hipMemcpyHostToDevice, e->stream));
-    *d_out = s->active.as<uint8_t>();
+    *d_out = s->aux.active;
     return TG_OK;
 }
 
@@ -105,10 +79,7 @@ static int pool_init(TgEngine* e, Search* s) {
     return TG_OK;
 }
 
-// tree_growth: how many times faster than one leaf per iteration a tree grows under the caller's schedule — the self-play
-// driver runs `rollouts` ITERATIONS per move whatever the batch, so its trees are `batch` times larger; a caller-driven search
-// decides its own iteration count (1).  Only the automatic pool size looks at it.
-static int search_alloc(TgEngine* e, const TgSearchConfig* cfg, size_t tree_growth = 1) {
+int search_alloc(TgEngine* e, const TgSearchConfig* cfg, size_t tree_growth) {
     if (!e) return fail(TG_ERR_INVALID_ARG, "null engine");
     if (!cfg || cfg->games <= 0 || cfg->games > e->cfg.max_batch) return fail(TG_ERR_INVALID_ARG, "games must be in 1..max_batch");
     const size_t B = cfg->batch ? cfg->batch : 1;  // virtual rollouts per tree and iteration
@@ -157,49 +128,52 @@ static int search_alloc(TgEngine* e, const TgSearchConfig* cfg, size_t tree_grow
     const size_t n_chunks = (pool_nodes >> chunk_shift) + 3 * G + 1;
     if ((n_chunks << chunk_shift) > ((size_t)1 << 32)) return fail(TG_ERR_INVALID_ARG, "node pool exceeds 2^32 nodes");
     const int cin_pad = e->cin_pad;
-    TG_HIP(s->hot.ensure((n_chunks << chunk_shift) * sizeof(NodeHot)));
-    TG_HIP(s->cold.ensure((n_chunks << chunk_shift) * sizeof(NodeCold)));
-    TG_HIP(s->root.ensure(G * 4));
-    TG_HIP(s->alloc.ensure(G * 8));
-    TG_HIP(s->chunk_head.ensure(G * 4));
-    TG_HIP(s->chunk_link.ensure(n_chunks * 4));
-    TG_HIP(s->chunk_fwd.ensure(n_chunks * 4));
-    TG_HIP(s->chunk_used.ensure(n_chunks * 4));
-    TG_HIP(s->free_ring.ensure(n_chunks * 4));
-    TG_HIP(s->pool_ctl.ensure(4 * 8));
-    TG_HIP(s->root_state.ensure(G * e->g.bytes));
-    TG_HIP(s->alive.ensure(G));
-    TG_HIP(s->abort.ensure(G));
-    TG_HIP(s->generation.ensure(G * 4));
-    TG_HIP(s->path_len.ensure(G * B * 4));
-    TG_HIP(s->path.ensure(G * B * MAX_DEPTH * 4));
-    TG_HIP(s->leaf_kind.ensure(G * B));
-    TG_HIP(s->leaf_rec.ensure(G * B * 8));
-    TG_HIP(s->child_pidx.ensure(G * B * EX_MOVES * 2));
-    TG_HIP(s->child_logit.ensure(G * B * EX_MOVES * 4));
+    // one line per device buffer: sized in elements of the field it is bound to
+    SearchDev& d = s->d;
+    SearchAux& x = s->aux;
+    TG_HIP(bind(s->hot, d.hot, n_chunks << chunk_shift));
+    TG_HIP(bind(s->cold, d.cold, n_chunks << chunk_shift));
+    TG_HIP(bind(s->root, d.root, G));
+    TG_HIP(bind(s->alloc, d.alloc, G * 2));
+    TG_HIP(bind(s->chunk_head, d.chunk_head, G));
+    TG_HIP(bind(s->chunk_link, d.chunk_link, n_chunks));
+    TG_HIP(bind(s->chunk_fwd, d.chunk_fwd, n_chunks));
+    TG_HIP(bind(s->chunk_used, d.chunk_used, n_chunks));
+    TG_HIP(bind(s->free_ring, d.free_ring, n_chunks));
+    TG_HIP(bind(s->pool_ctl, d.pool_ctl, 4));
+    TG_HIP(bind(s->root_state, d.root_state, G * e->g.bytes));
+    TG_HIP(bind(s->alive, d.alive, G));
+    TG_HIP(bind(s->abort, d.abort, G));
+    TG_HIP(bind(s->generation, d.generation, G));
+    TG_HIP(bind(s->path_len, d.path_len, G * B));
+    TG_HIP(bind(s->path, d.path, G * B * MAX_DEPTH));
+    TG_HIP(bind(s->leaf_kind, d.leaf_kind, G * B));
+    TG_HIP(bind(s->leaf_rec, d.leaf_rec, G * B * 2));
+    TG_HIP(bind(s->child_pidx, d.child_pidx, G * B * EX_MOVES));
+    TG_HIP(bind(s->child_logit, x.child_logit, G * B * EX_MOVES));
     TG_HIP(hipMemsetAsync(s->leaf_rec.p, 0, G * B * 8, e->stream));
-    TG_HIP(s->leaf_hash.ensure(G * B * 8));
-    TG_HIP(s->op.ensure(G * 4));
-    TG_HIP(s->active.ensure(G));
-    TG_HIP(s->noise.ensure(G * EX_MOVES * 4));
-    TG_HIP(s->err.ensure(4));
-    TG_HIP(s->counters.ensure(G * 16));
-    TG_HIP(s->r_moves.ensure(G * EX_MOVES * 2));
-    TG_HIP(s->r_visits.ensure(G * EX_MOVES * 4));
-    TG_HIP(s->r_prior.ensure(G * EX_MOVES * 4));
-    TG_HIP(s->r_q.ensure(G * EX_MOVES * 4));
-    TG_HIP(s->r_counts.ensure(G * 4));
-    TG_HIP(s->r_rv.ensure(G * 4));
-    TG_HIP(s->r_rq.ensure(G * 4));
-    TG_HIP(s->s_moves.ensure(G * 2));
+    TG_HIP(bind(s->leaf_hash, d.leaf_hash, G * B));
+    TG_HIP(bind(s->op, x.op, G));
+    TG_HIP(bind(s->active, x.active, G));
+    TG_HIP(bind(s->noise, x.noise, G * EX_MOVES));
+    TG_HIP(bind(s->err, d.err, 1));
+    TG_HIP(bind(s->counters, d.counters, G * 2));
+    TG_HIP(bind(s->r_moves, x.r_moves, G * EX_MOVES));
+    TG_HIP(bind(s->r_visits, x.r_visits, G * EX_MOVES));
+    TG_HIP(bind(s->r_prior, x.r_prior, G * EX_MOVES));
+    TG_HIP(bind(s->r_q, x.r_q, G * EX_MOVES));
+    TG_HIP(bind(s->r_counts, x.r_counts, G));
+    TG_HIP(bind(s->r_rv, x.r_rv, G));
+    TG_HIP(bind(s->r_rq, x.r_rq, G));
+    TG_HIP(bind(s->s_moves, x.s_moves, G));
     if (e->cfg.evaluator == TG_EVAL_RESNET) {
         if (net_takes_states(e)) {
-            TG_HIP(s->leaf_state.ensure(G * B * e->g.bytes));
+            TG_HIP(bind(s->leaf_state, d.leaf_state, G * B * e->g.bytes));
             TG_HIP(hipMemsetAsync(s->leaf_state.p, 0, s->leaf_state.bytes, e->stream));
         } else
-        TG_HIP(s->planes.ensure(G * B * e->g.nsq * cin_pad * 4));
-        TG_HIP(s->policy.ensure(G * B * (size_t)e->policy_size * 4));
-        TG_HIP(s->eval.ensure(G * B * 4));
+        TG_HIP(bind(s->planes, d.planes, G * B * e->g.nsq * cin_pad));
+        TG_HIP(bind(s->policy, d.policy, G * B * (size_t)e->policy_size));
+        TG_HIP(bind(s->eval, d.eval, G * B));
         if (s->planes.p) TG_HIP(hipMemsetAsync(s->planes.p, 0, s->planes.bytes, e->stream));
     }
     // exploration_rate(n) = ln((1 + n + base) / base) + init for integer visit counts (mcts.rs:10-12),
@@ -210,29 +184,15 @@ static int search_alloc(TgEngine* e, const TgSearchConfig* cfg, size_t tree_grow
         float nf = (float)i;
         ctab[i] = logf((1.0f + nf + cfg->exploration_base) / cfg->exploration_base) + cfg->exploration_init;
     }
-    TG_HIP(s->ctab.ensure((size_t)ctab_size * 4));
+    TG_HIP(bind(s->ctab, d.ctab, (size_t)ctab_size));
     TG_HIP(hipMemcpy(s->ctab.p, ctab.data(), (size_t)ctab_size * 4, hipMemcpyHostToDevice));
     TG_HIP(hipMemsetAsync(s->err.p, 0, 4, e->stream));
     TG_HIP(hipMemsetAsync(s->counters.p, 0, G * 16, e->stream));
     TG_HIP(hipMemsetAsync(s->generation.p, 0, G * 4, e->stream));
     TG_HIP(hipMemsetAsync(s->alive.p, 0, G, e->stream));
     TG_HIP(hipMemsetAsync(s->abort.p, 0, G, e->stream));
-    SearchDev& d = s->d;
-    d.hot = s->hot.as<NodeHot>(); d.cold = s->cold.as<NodeCold>(); d.root = s->root.as<uint32_t>(); d.alloc = s->alloc.as<uint32_t>();
-    d.chunk_head = s->chunk_head.as<uint32_t>(); d.chunk_link = s->chunk_link.as<uint32_t>(); d.chunk_fwd = s->chunk_fwd.as<uint32_t>();
-    d.chunk_used = s->chunk_used.as<uint32_t>(); d.free_ring = s->free_ring.as<uint32_t>();
-    d.pool_ctl = s->pool_ctl.as<unsigned long long>(); d.n_chunks = (uint32_t)n_chunks; d.chunk_shift = chunk_shift;
-    d.root_state = s->root_state.as<uint8_t>(); d.alive = s->alive.as<uint8_t>(); d.abort = s->abort.as<uint8_t>(); d.generation = s->generation.as<uint32_t>();
-    d.path_len = s->path_len.as<int32_t>(); d.path = s->path.as<uint32_t>(); d.leaf_kind = s->leaf_kind.as<uint8_t>();
-    d.leaf_rec = s->leaf_rec.as<uint32_t>(); d.child_pidx = s->child_pidx.as<uint16_t>();
-    d.leaf_hash = s->leaf_hash.as<uint64_t>(); d.planes = s->planes.as<float>(); d.leaf_state = s->leaf_state.as<uint8_t>();
-    d.policy = s->policy.as<float>();
-    d.eval = s->eval.as<float>(); d.ctab = s->ctab.as<float>(); d.lut5 = e->lut5.as<int16_t>(); d.err = s->err.as<uint32_t>();
-    d.counters = s->counters.as<unsigned long long>();
-    {
-        int prc = pool_init(e, s);
-        if (prc) return prc;
-    }
+    d.n_chunks = (uint32_t)n_chunks; d.chunk_shift = chunk_shift; d.lut5 = e->lut5.as<int16_t>();
+    if (int rc = pool_init(e, s)) return rc;
     d.G = cfg->games; d.n = e->g.n; d.cin_pad = cin_pad; d.P = e->policy_size; d.ctab_size = ctab_size;
     d.legacy5 = e->legacy5 ? 1 : 0; d.evaluator = e->cfg.evaluator; d.slot_base = cfg->slot_base; d.seed = cfg->seed;
     d.batch = (int)B; d.pass = 0;
@@ -242,13 +202,12 @@ static int search_alloc(TgEngine* e, const TgSearchConfig* cfg, size_t tree_grow
     return TG_OK;
 }
 
-// every tree = Node::default(), every game alive with the given root state
-static int search_reset_trees(TgEngine* e) {
+int search_reset_trees(TgEngine* e) {
     Search* s = e->search;
     const size_t G = (size_t)s->d.G;
     std::vector<int32_t> op(G, -2);
     TG_HIP(hipMemcpyAsync(s->op.p, op.data(), G * 4, hipMemcpyHostToDevice, e->stream));
-    launch_reroot(e->stream, s->d, s->op.as<int32_t>());
+    launch_reroot(e->stream, s->d, s->aux.op);
     TG_HIP(hipGetLastError());
     TG_HIP(hipStreamSynchronize(e->stream));
     return TG_OK;
@@ -257,9 +216,9 @@ static int search_reset_trees(TgEngine* e) {
 // FC-head networks: the backup reads the network's logits buffer directly (softmax statistics and tanh in the tree kernel,
 // softmax.cuh).  Bound per call: the weights may have been re-finalised (tg_train_commit, another precision) since the
 // search was created.
-// `leaves`: rows of the forwards that follow (0 = games × batch; a compacted iteration passes count × batch — whether the FC
+// `leaves`: rows of the forwards that follow (games × batch; a compacted iteration passes count × batch — whether the FC
 // serves the gather depends on the batch, the bits do not)
-static void bind_logits(TgEngine* e, int leaves = 0) {
+static void bind_logits(TgEngine* e, int leaves) {
     Search* s = e->search;
     s->d.logits = nullptr;
     s->d.logit_ld = 0;
@@ -277,10 +236,10 @@ static void bind_logits(TgEngine* e, int leaves = 0) {
         const float* fs = net_fc_stats(e, &blocks, &stride);
         if (fs) { s->d.fc_stats = fs; s->d.fc_blocks = blocks; s->d.fc_stride = stride; }
         // exact-f32 FC at a batch its ring kernel serves: the FC's epilogue hands the backup the children's logits directly
-        if (fs && !s->d.planes && net_gather_ok(e, leaves ? leaves : s->d.G * s->d.batch)) {
-            const FcGatherArgs g{s->d.child_pidx, s->d.leaf_rec, s->child_logit.as<float>(), EX_MOVES};
+        if (fs && !s->d.planes && net_gather_ok(e, leaves)) {
+            const FcGatherArgs g{s->d.child_pidx, s->d.leaf_rec, s->aux.child_logit, EX_MOVES};
             net_set_gather(e, &g);
-            s->d.child_logit = s->child_logit.as<float>();
+            s->d.child_logit = s->aux.child_logit;
         }
     }
 }
@@ -292,90 +251,41 @@ struct GatherScope {
     ~GatherScope() { net_set_gather(e, nullptr); }
 };
 
-// one lock-step iteration: the body of train/src/self_play.rs:181-210
-static int search_iterate(TgEngine* e, const uint8_t* d_active) {
+// `iters` lock-step iterations, each the body of train/src/self_play.rs:181-210.  `batch` virtual rollouts per tree (Player's
+// batching model, alpha-tak/src/player.rs:77-93) run back to back inside the select kernel (a game's tree belongs to one wave),
+// then ONE network batch of games × batch leaves, then the de-virtualisations in the same order inside the backup kernel.
+//   d_active given:  select(mask) | net | backup, per iteration — the fused kernels take no mask
+//   otherwise:       select(0) | net | backup(0)+select(1) | net | … | backup(iters-1): one tree kernel per iteration
+//   list given:      the same over the compacted list of `count` games (0 < count < G): wave w serves list[w], leaf slots
+//                    w·batch + pass, the network on count × batch leaves
+int search_iterate(TgEngine* e, int iters, const uint8_t* d_active, const int32_t* list, int count) {
     Search* s = e->search;
-    bind_logits(e);
-    GatherScope scope{e};
-    // `batch` virtual rollouts per tree (Player's batching model, alpha-tak/src/player.rs:77-93) run back to back inside the
-    // select kernel (a game's tree belongs to one wave), then ONE network batch of games × batch leaves, then the
-    // de-virtualisations in the same order inside the backup kernel
-    SearchDev d = s->d;
-    d.pass = s->d.batch > 1 ? -1 : 0;  // -1: the kernel runs the `batch` passes of a game back to back in that game's wave
-    launch_select(e->stream, d, d_active);
-    TG_HIP(hipGetLastError());
-    if (e->cfg.evaluator == TG_EVAL_RESNET) {
-        const int leaves = s->d.G * s->d.batch;
-        float* pol = s->d.logits ? nullptr : s->d.policy;  // logits mode: the backup takes softmax / tanh itself
-        int rc = s->d.planes ? net_forward_dev(e, leaves, s->d.planes, pol, s->d.eval)
-                             : net_forward_states_dev(e, leaves, s->d.leaf_state, pol, s->d.eval);
-        if (rc) return rc;
-    }
-    launch_backup(e->stream, d);
-    TG_HIP(hipGetLastError());
-    return TG_OK;
-}
-
-static int search_iterate_many(TgEngine* e, int iters) {
-    Search* s = e->search;
-    if (iters <= 0) return TG_OK;
-    bind_logits(e);
-    GatherScope scope{e};
-    if (iters > 1) {
-        // select(0) | net | backup(0)+select(1) | net | … | backup(iters-1): one tree kernel per iteration.  With `batch` > 1
-        // every one of them runs all the passes of a game back to back in that game's wave (leaf slot g·batch + pass), and the
-        // network sees games × batch leaves per call
-        SearchDev d = s->d;
-        d.pass = s->d.batch > 1 ? -1 : 0;
-        const int leaves = s->d.G * s->d.batch;
-        launch_select(e->stream, d, nullptr);
-        for (int i = 0; i < iters; i++) {
-            if (e->cfg.evaluator == TG_EVAL_RESNET) {
-                float* pol = s->d.logits ? nullptr : s->d.policy;
-                int rc = s->d.planes ? net_forward_dev(e, leaves, s->d.planes, pol, s->d.eval)
-                                     : net_forward_states_dev(e, leaves, s->d.leaf_state, pol, s->d.eval);
-                if (rc) return rc;
-            }
-            if (i + 1 < iters) launch_backup_select(e->stream, d);
-            else launch_backup(e->stream, d);
-        }
-        TG_HIP(hipGetLastError());
-        return TG_OK;
-    }
-    for (int i = 0; i < iters; i++) {
-        int rc = search_iterate(e, nullptr);
-        if (rc) return rc;
-    }
-    return TG_OK;
-}
-
-// `iters` iterations over the compacted list of `count` games (0 < count < G), fused like search_iterate_many:
-// select | net | backup+select | … | backup, one tree kernel per iteration, the network on count × batch leaves
-static int search_iterate_list(TgEngine* e, int iters, int count) {
-    Search* s = e->search;
-    if (iters <= 0 || count <= 0) return TG_OK;
-    const int leaves = count * s->d.batch;
+    if (iters <= 0 || (list && count <= 0)) return TG_OK;
+    const int leaves = (list ? count : s->d.G) * s->d.batch;
     bind_logits(e, leaves);
     GatherScope scope{e};
     SearchDev d = s->d;
-    d.pass = s->d.batch > 1 ? -1 : 0;
-    const int32_t* list = s->boost_list.as<int32_t>();
-    launch_select_list(e->stream, d, list, count);
+    d.pass = d.batch > 1 ? -1 : 0;  // -1: the kernel runs the `batch` passes of a game back to back in that game's wave
+    hipStream_t st = e->stream;
     for (int i = 0; i < iters; i++) {
+        if (i == 0 || d_active) {
+            if (list) launch_select_list(st, d, list, count);
+            else launch_select(st, d, d_active);
+        }
         if (e->cfg.evaluator == TG_EVAL_RESNET) {
-            float* pol = s->d.logits ? nullptr : s->d.policy;
-            int rc = s->d.planes ? net_forward_dev(e, leaves, s->d.planes, pol, s->d.eval)
-                                 : net_forward_states_dev(e, leaves, s->d.leaf_state, pol, s->d.eval);
+            float* pol = d.logits ? nullptr : d.policy;  // logits mode: the backup takes softmax / tanh itself
+            int rc = d.planes ? net_forward_dev(e, leaves, d.planes, pol, d.eval) : net_forward_states_dev(e, leaves, d.leaf_state, pol, d.eval);
             if (rc) return rc;
         }
-        if (i + 1 < iters) launch_backup_select_list(e->stream, d, list, count);
-        else launch_backup_list(e->stream, d, list, count);
+        const bool last = d_active || i + 1 == iters;  // (nothing follows, or the next select needs the mask)
+        if (list) last ? launch_backup_list(st, d, list, count) : launch_backup_select_list(st, d, list, count);
+        else last ? launch_backup(st, d) : launch_backup_select(st, d);
     }
     TG_HIP(hipGetLastError());
     return TG_OK;
 }
 
-static int read_counters(TgEngine* e, unsigned long long* expansions, unsigned long long* evals) {
+int read_counters(TgEngine* e, unsigned long long* expansions, unsigned long long* evals) {
     Search* s = e->search;
     std::vector<unsigned long long> h((size_t)s->d.G * 2);
     TG_HIP(hipMemcpy(h.data(), s->counters.p, h.size() * 8, hipMemcpyDeviceToHost));
@@ -386,9 +296,16 @@ static int read_counters(TgEngine* e, unsigned long long* expansions, unsigned l
     return TG_OK;
 }
 
-static int sync_and_check(TgEngine* e) {
+int sync_and_check(TgEngine* e) {
     TG_HIP(hipStreamSynchronize(e->stream));
     return search_poll_errors(e);
+}
+
+// read-back of an optional output: `n` elements of its type; nothing for a null destination or an empty range
+template <class T, class U>
+static hipError_t copy_out(T* dst, const U* src, size_t n) {
+    static_assert(sizeof(T) == sizeof(U), "host and device element differ");
+    return dst && n ? hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
 }
 
 }  // namespace tg
@@ -398,9 +315,7 @@ using namespace tg;
 extern "C" {
 
 int tg_search_create(TgEngine* e, const TgSearchConfig* cfg) {
-    int rc = search_alloc(e, cfg);
-    if (rc) return rc;
-    return TG_OK;
+    return search_alloc(e, cfg);
 }
 
 int tg_search_reset(TgEngine* e, const void* states) {
@@ -426,9 +341,7 @@ int tg_search_run(TgEngine* e, int iters, const uint8_t* active) {
     const uint8_t* d_active;
     rc = upload_mask(e, active, &d_active);
     if (rc) return rc;
-    if (!d_active) rc = search_iterate_many(e, iters);
-    else
-        for (int i = 0; i < iters && !rc; i++) rc = search_iterate(e, d_active);
+    rc = search_iterate(e, iters, d_active);
     if (rc) return rc;
     if (active) TG_HIP(hipStreamSynchronize(e->stream));  // the staged mask must outlive the launches
     return TG_OK;
@@ -454,7 +367,7 @@ int tg_search_apply_noise(TgEngine* e, const float* noise, float ratio, const ui
     rc = upload_mask(e, active, &d_active);
     if (rc) return rc;
     TG_HIP(hipMemcpyAsync(s->noise.p, noise, (size_t)s->d.G * EX_MOVES * 4, hipMemcpyHostToDevice, e->stream));
-    launch_apply_noise(e->stream, s->d, d_active, s->noise.as<float>(), ratio);
+    launch_apply_noise(e->stream, s->d, d_active, s->aux.noise, ratio);
     TG_HIP(hipGetLastError());
     return sync_and_check(e);
 }
@@ -464,23 +377,23 @@ int tg_search_root(TgEngine* e, TgMove* moves, uint32_t* visits, float* prior, f
     int rc = need_search(e);
     if (rc) return rc;
     Search* s = e->search;
-    const size_t G = (size_t)s->d.G;
-    TG_HIP(hipMemsetAsync(s->r_moves.p, 0, G * EX_MOVES * 2, e->stream));
-    TG_HIP(hipMemsetAsync(s->r_visits.p, 0, G * EX_MOVES * 4, e->stream));
-    TG_HIP(hipMemsetAsync(s->r_prior.p, 0, G * EX_MOVES * 4, e->stream));
-    TG_HIP(hipMemsetAsync(s->r_q.p, 0, G * EX_MOVES * 4, e->stream));
-    launch_root_stats(e->stream, s->d, s->r_moves.as<uint16_t>(), s->r_visits.as<uint32_t>(), s->r_prior.as<float>(), s->r_q.as<float>(),
-                      s->r_counts.as<int32_t>(), s->r_rv.as<uint32_t>(), s->r_rq.as<float>());
+    const SearchAux& x = s->aux;
+    const size_t G = (size_t)s->d.G, R = G * EX_MOVES;
+    TG_HIP(hipMemsetAsync(x.r_moves, 0, R * sizeof *x.r_moves, e->stream));
+    TG_HIP(hipMemsetAsync(x.r_visits, 0, R * sizeof *x.r_visits, e->stream));
+    TG_HIP(hipMemsetAsync(x.r_prior, 0, R * sizeof *x.r_prior, e->stream));
+    TG_HIP(hipMemsetAsync(x.r_q, 0, R * sizeof *x.r_q, e->stream));
+    launch_root_stats(e->stream, s->d, x.r_moves, x.r_visits, x.r_prior, x.r_q, x.r_counts, x.r_rv, x.r_rq);
     TG_HIP(hipGetLastError());
     rc = sync_and_check(e);
     if (rc) return rc;
-    if (moves) TG_HIP(hipMemcpy(moves, s->r_moves.p, G * EX_MOVES * 2, hipMemcpyDeviceToHost));
-    if (visits) TG_HIP(hipMemcpy(visits, s->r_visits.p, G * EX_MOVES * 4, hipMemcpyDeviceToHost));
-    if (prior) TG_HIP(hipMemcpy(prior, s->r_prior.p, G * EX_MOVES * 4, hipMemcpyDeviceToHost));
-    if (q) TG_HIP(hipMemcpy(q, s->r_q.p, G * EX_MOVES * 4, hipMemcpyDeviceToHost));
-    if (counts) TG_HIP(hipMemcpy(counts, s->r_counts.p, G * 4, hipMemcpyDeviceToHost));
-    if (root_visits) TG_HIP(hipMemcpy(root_visits, s->r_rv.p, G * 4, hipMemcpyDeviceToHost));
-    if (root_q) TG_HIP(hipMemcpy(root_q, s->r_rq.p, G * 4, hipMemcpyDeviceToHost));
+    TG_HIP(copy_out(moves, x.r_moves, R));
+    TG_HIP(copy_out(visits, x.r_visits, R));
+    TG_HIP(copy_out(prior, x.r_prior, R));
+    TG_HIP(copy_out(q, x.r_q, R));
+    TG_HIP(copy_out(counts, x.r_counts, G));
+    TG_HIP(copy_out(root_visits, x.r_rv, G));
+    TG_HIP(copy_out(root_q, x.r_rq, G));
     return TG_OK;
 }
 
@@ -499,33 +412,31 @@ int tg_search_debug(TgEngine* e, int depth, int top_k, TgMove* moves, uint32_t* 
     // the device scratch of one slice of games stays within TG_DEBUG_SCRATCH_BYTES (≤ 200 KB per game: at least 300 games a slice)
     const size_t per_game = EX_MOVES * (2 + 4 + 4 + 4) + 4 + 4 + K * D * (2 + 4) + K * 4;
     const size_t slice = std::max<size_t>(1, std::min<size_t>(G, (size_t)TG_DEBUG_SCRATCH_BYTES / per_game));
-    TG_HIP(s->dbg_moves.ensure(slice * EX_MOVES * 2));
-    TG_HIP(s->dbg_visits.ensure(slice * EX_MOVES * 4));
-    TG_HIP(s->dbg_reward.ensure(slice * EX_MOVES * 4));
-    TG_HIP(s->dbg_policy.ensure(slice * EX_MOVES * 4));
-    TG_HIP(s->dbg_counts.ensure(slice * 4));
-    TG_HIP(s->dbg_eval.ensure(slice * 4));
-    TG_HIP(s->dbg_cmoves.ensure(std::max<size_t>(1, slice * K * D * 2)));
-    TG_HIP(s->dbg_cvisits.ensure(std::max<size_t>(1, slice * K * D * 4)));
-    TG_HIP(s->dbg_clen.ensure(std::max<size_t>(1, slice * K * 4)));
-    DebugOut o{s->dbg_moves.as<uint16_t>(), s->dbg_visits.as<uint32_t>(), s->dbg_reward.as<float>(), s->dbg_policy.as<float>(),
-               s->dbg_counts.as<int32_t>(), s->dbg_eval.as<float>(), s->dbg_cmoves.as<uint16_t>(), s->dbg_cvisits.as<uint32_t>(),
-               s->dbg_clen.as<int32_t>()};
+    DebugOut o{};
+    TG_HIP(bind(s->dbg_moves, o.moves, slice * EX_MOVES));
+    TG_HIP(bind(s->dbg_visits, o.visits, slice * EX_MOVES));
+    TG_HIP(bind(s->dbg_reward, o.reward, slice * EX_MOVES));
+    TG_HIP(bind(s->dbg_policy, o.policy, slice * EX_MOVES));
+    TG_HIP(bind(s->dbg_counts, o.counts, slice));
+    TG_HIP(bind(s->dbg_eval, o.eval, slice));
+    TG_HIP(bind(s->dbg_cmoves, o.cont_moves, std::max<size_t>(1, slice * K * D)));  // (never an empty allocation)
+    TG_HIP(bind(s->dbg_cvisits, o.cont_visits, std::max<size_t>(1, slice * K * D)));
+    TG_HIP(bind(s->dbg_clen, o.cont_len, std::max<size_t>(1, slice * K)));
     for (size_t g0 = 0; g0 < G; g0 += slice) {
         const size_t ns = std::min(slice, G - g0);
         launch_search_debug(e->stream, s->d, (int)g0, (int)ns, depth, (int)K, o);
         TG_HIP(hipGetLastError());
         TG_HIP(hipStreamSynchronize(e->stream));
         const size_t R = g0 * EX_MOVES, C = g0 * K * D;
-        if (moves) TG_HIP(hipMemcpy(moves + R, o.moves, ns * EX_MOVES * 2, hipMemcpyDeviceToHost));
-        if (visits) TG_HIP(hipMemcpy(visits + R, o.visits, ns * EX_MOVES * 4, hipMemcpyDeviceToHost));
-        if (reward) TG_HIP(hipMemcpy(reward + R, o.reward, ns * EX_MOVES * 4, hipMemcpyDeviceToHost));
-        if (policy) TG_HIP(hipMemcpy(policy + R, o.policy, ns * EX_MOVES * 4, hipMemcpyDeviceToHost));
-        if (counts) TG_HIP(hipMemcpy(counts + g0, o.counts, ns * 4, hipMemcpyDeviceToHost));
-        if (eval) TG_HIP(hipMemcpy(eval + g0, o.eval, ns * 4, hipMemcpyDeviceToHost));
-        if (K * D && cont_moves) TG_HIP(hipMemcpy(cont_moves + C, o.cont_moves, ns * K * D * 2, hipMemcpyDeviceToHost));
-        if (K * D && cont_visits) TG_HIP(hipMemcpy(cont_visits + C, o.cont_visits, ns * K * D * 4, hipMemcpyDeviceToHost));
-        if (K && cont_len) TG_HIP(hipMemcpy(cont_len + g0 * K, o.cont_len, ns * K * 4, hipMemcpyDeviceToHost));
+        TG_HIP(copy_out(moves ? moves + R : nullptr, o.moves, ns * EX_MOVES));
+        TG_HIP(copy_out(visits ? visits + R : nullptr, o.visits, ns * EX_MOVES));
+        TG_HIP(copy_out(reward ? reward + R : nullptr, o.reward, ns * EX_MOVES));
+        TG_HIP(copy_out(policy ? policy + R : nullptr, o.policy, ns * EX_MOVES));
+        TG_HIP(copy_out(counts ? counts + g0 : nullptr, o.counts, ns));
+        TG_HIP(copy_out(eval ? eval + g0 : nullptr, o.eval, ns));
+        TG_HIP(copy_out(cont_moves ? cont_moves + C : nullptr, o.cont_moves, ns * K * D));
+        TG_HIP(copy_out(cont_visits ? cont_visits + C : nullptr, o.cont_visits, ns * K * D));
+        TG_HIP(copy_out(cont_len ? cont_len + g0 * K : nullptr, o.cont_len, ns * K));
     }
     return TG_OK;
 }
@@ -539,8 +450,8 @@ int tg_search_play(TgEngine* e, const TgMove* moves, const uint8_t* active) {
     rc = upload_mask(e, active, &d_active);
     if (rc) return rc;
     TG_HIP(hipMemcpyAsync(s->s_moves.p, moves, (size_t)s->d.G * 2, hipMemcpyHostToDevice, e->stream));
-    launch_play_move(e->stream, s->d, s->s_moves.as<uint16_t>(), d_active, s->op.as<int32_t>());
-    launch_reroot(e->stream, s->d, s->op.as<int32_t>());
+    launch_play_move(e->stream, s->d, s->aux.s_moves, d_active, s->aux.op);
+    launch_reroot(e->stream, s->d, s->aux.op);
     TG_HIP(hipGetLastError());
     return sync_and_check(e);
 }
@@ -564,8 +475,8 @@ int tg_search_dump(TgEngine* e, int game, TgNodeRecord* records, size_t capacity
     if (rc) return rc;
     // gather the game's chunks (its chain through chunk_link) and index the tree by pool index
     uint32_t root = 0, head = 0;
-    TG_HIP(hipMemcpy(&root, s->root.as<uint32_t>() + game, 4, hipMemcpyDeviceToHost));
-    TG_HIP(hipMemcpy(&head, s->chunk_head.as<uint32_t>() + game, 4, hipMemcpyDeviceToHost));
+    TG_HIP(hipMemcpy(&root, s->d.root + game, 4, hipMemcpyDeviceToHost));
+    TG_HIP(hipMemcpy(&head, s->d.chunk_head + game, 4, hipMemcpyDeviceToHost));
     std::vector<uint32_t> link(s->d.n_chunks);
     TG_HIP(hipMemcpy(link.data(), s->chunk_link.p, (size_t)s->d.n_chunks * 4, hipMemcpyDeviceToHost));
     const int sh = s->d.chunk_shift;
@@ -578,8 +489,8 @@ int tg_search_dump(TgEngine* e, int game, TgNodeRecord* records, size_t capacity
         where[c] = hot_h.size();
         hot_h.resize(hot_h.size() + CH);
         cold_h.resize(cold_h.size() + CH);
-        TG_HIP(hipMemcpy(hot_h.data() + where[c], s->hot.as<NodeHot>() + ((size_t)c << sh), CH * sizeof(NodeHot), hipMemcpyDeviceToHost));
-        TG_HIP(hipMemcpy(cold_h.data() + where[c], s->cold.as<NodeCold>() + ((size_t)c << sh), CH * sizeof(NodeCold), hipMemcpyDeviceToHost));
+        TG_HIP(hipMemcpy(hot_h.data() + where[c], s->d.hot + ((size_t)c << sh), CH * sizeof(NodeHot), hipMemcpyDeviceToHost));
+        TG_HIP(hipMemcpy(cold_h.data() + where[c], s->d.cold + ((size_t)c << sh), CH * sizeof(NodeCold), hipMemcpyDeviceToHost));
     }
     bool corrupt = false;
     auto at = [&](uint32_t nd) -> size_t {
@@ -665,236 +576,4 @@ int tg_search_pool(TgEngine* e, uint64_t* nodes_total, uint64_t* nodes_in_use, u
     if (nodes_peak) *nodes_peak = (uint64_t)ctl[3] << s->d.chunk_shift;
     return TG_OK;
 }
-
-// ---- self-play -----------------------------------------------------------------------------------
-
-int tg_selfplay_create(TgEngine* e, const TgSearchConfig* scfg, const TgSelfPlayConfig* cfg) {
-    if (!cfg || !scfg) return fail(TG_ERR_INVALID_ARG, "null self-play config");
-    if (cfg->rollouts < 1 || cfg->max_examples < 1) return fail(TG_ERR_INVALID_ARG, "rollouts and max_examples must be positive");
-    if (cfg->max_game_plies < 0 || cfg->max_game_plies > TG_LIMIT_GAME_PLIES)
-        return fail(TG_ERR_INVALID_ARG, "max_game_plies must be 0 (= TG_LIMIT_GAME_PLIES) or in 1..TG_LIMIT_GAME_PLIES");
-    // virtual rollouts per game and iteration: TgSelfPlayConfig.batch (0 = 1: self_play_parallel's one leaf per game,
-    // self_play.rs:181-210; > 1: Player's batching as train/src/self_play.rs:21-92 uses it).  TgSearchConfig.batch is ignored.
-    if (cfg->batch < 0) return fail(TG_ERR_INVALID_ARG, "TgSelfPlayConfig.batch must be in 0..4096 (0 = 1)");
-    if (cfg->batch > 4096) return fail(TG_ERR_INVALID_ARG, "TgSelfPlayConfig.batch must be at most 4096 virtual rollouts per game and iteration");
-    const int B = cfg->batch ? cfg->batch : 1;
-    if (e && scfg->games > 0 && e->cfg.evaluator == TG_EVAL_RESNET && (long long)scfg->games * B > (long long)e->cfg.max_batch)
-        return fail(TG_ERR_INVALID_ARG, "games x batch = " + std::to_string((long long)scfg->games * B) +
-                                            " leaves per iteration exceed max_batch = " + std::to_string(e->cfg.max_batch));
-    TgSearchConfig sc1 = *scfg;
-    sc1.batch = (uint32_t)B;
-    int rc = search_alloc(e, &sc1, (size_t)B);
-    if (rc) return rc;
-    Search* s = e->search;
-    s->selfplay = true;
-    s->spcfg = *cfg;
-    s->d.retire = 1;
-    const size_t G = (size_t)s->d.G, sb = (size_t)e->g.bytes;
-    const int epg = TG_LIMIT_GAME_PLIES;
-    const size_t ME = (size_t)cfg->max_examples;
-    TG_HIP(s->st_hdr.ensure(G * epg * sizeof(ExampleRec)));
-    TG_HIP(s->st_state.ensure(G * epg * sb));
-    TG_HIP(s->st_moves.ensure(G * epg * EX_MOVES * 2));
-    TG_HIP(s->st_visits.ensure(G * epg * EX_MOVES * 4));
-    TG_HIP(s->st_count.ensure(G * 4));
-    TG_HIP(s->out_hdr.ensure(ME * sizeof(ExampleRec)));
-    TG_HIP(s->out_state.ensure(ME * sb));
-    TG_HIP(s->out_moves.ensure(ME * EX_MOVES * 2));
-    TG_HIP(s->out_visits.ensure(ME * EX_MOVES * 4));
-    TG_HIP(s->fin.ensure(G));
-    TG_HIP(s->recycle.ensure(G));
-    TG_HIP(s->out_off.ensure(G * 4));
-    TG_HIP(s->chosen.ensure(G * 4));
-    TG_HIP(s->mask.ensure(G));
-    TG_HIP(s->stats.ensure(ST_COUNT * 8));
-    TG_HIP(hipMemsetAsync(s->st_count.p, 0, G * 4, e->stream));
-    TG_HIP(hipMemsetAsync(s->stats.p, 0, ST_COUNT * 8, e->stream));
-    TG_HIP(hipMemsetAsync(s->fin.p, 0, G, e->stream));
-    TG_HIP(s->boost_list.ensure(G * 4));
-    TG_HIP(s->boost_count.ensure(4));
-    TG_HIP(hipHostMalloc((void**)&s->h_boost_count, 4, hipHostMallocDefault));
-    *s->h_boost_count = 0;
-    SelfPlayDev& p = s->p;
-    p.st_hdr = s->st_hdr.as<ExampleRec>(); p.st_state = s->st_state.as<uint8_t>(); p.st_moves = s->st_moves.as<uint16_t>();
-    p.st_visits = s->st_visits.as<uint32_t>(); p.st_count = s->st_count.as<int32_t>();
-    p.out_hdr = s->out_hdr.as<ExampleRec>(); p.out_state = s->out_state.as<uint8_t>(); p.out_moves = s->out_moves.as<uint16_t>();
-    p.out_visits = s->out_visits.as<uint32_t>();
-    p.fin = s->fin.as<uint8_t>(); p.recycle = s->recycle.as<uint8_t>(); p.out_off = s->out_off.as<uint32_t>();
-    p.chosen = s->chosen.as<int32_t>(); p.mask = s->mask.as<uint8_t>(); p.stats = s->stats.as<unsigned long long>();
-    p.ex_per_game = epg; p.max_examples = cfg->max_examples;
-    p.max_game_plies = cfg->max_game_plies ? cfg->max_game_plies : epg;
-    p.rollouts = cfg->rollouts; p.noise_plies = cfg->noise_plies; p.exploit_plies = cfg->exploit_plies; p.komi = cfg->komi;
-    p.total_games = cfg->total_games; p.noise_alpha = cfg->noise_alpha; p.noise_ratio = cfg->noise_ratio;
-    // games[i] = Game::with_komi(komi), nodes[i] = Node::default()  (self_play.rs:102-103)
-    std::vector<uint8_t> start(sb, 0);
-    {
-        int stones, caps;
-        starting_stones(e->g.n, stones, caps);
-        TgHeader* h = (TgHeader*)(start.data() + sb - sizeof(TgHeader));
-        h->n = (uint8_t)e->g.n; h->to_move = 0; h->ply = 0;
-        h->white_stones = h->black_stones = (uint8_t)stones;
-        h->white_caps = h->black_caps = (uint8_t)caps;
-        h->half_komi = (int8_t)(cfg->komi * 2); h->reversible_plies = 0;
-    }
-    std::vector<uint8_t> all(G * sb);
-    for (size_t g = 0; g < G; g++) std::memcpy(&all[g * sb], start.data(), sb);
-    TG_HIP(hipMemcpy(s->root_state.p, all.data(), all.size(), hipMemcpyHostToDevice));
-    TG_HIP(hipMemsetAsync(s->alive.p, 1, G, e->stream));
-    return search_reset_trees(e);
-}
-
-int tg_selfplay_set_schedule(TgEngine* e, const TgRolloutSchedule* sc) {
-    int rc = need_search(e);
-    if (rc) return rc;
-    Search* s = e->search;
-    if (!s->selfplay) return fail(TG_ERR_STATE, "tg_selfplay_set_schedule: tg_selfplay_create has not been called");
-    if (s->stepped) return fail(TG_ERR_STATE, "tg_selfplay_set_schedule: the schedule is fixed once tg_selfplay_step has run");
-    if (!sc) return fail(TG_ERR_INVALID_ARG, "tg_selfplay_set_schedule: null schedule");
-    if (sc->boost_plies < 0 || sc->boost_plies > TG_LIMIT_GAME_PLIES)
-        return fail(TG_ERR_INVALID_ARG, "TgRolloutSchedule.boost_plies must be in 0..TG_LIMIT_GAME_PLIES");
-    if (sc->boost_factor < 1 || sc->boost_factor > 64) return fail(TG_ERR_INVALID_ARG, "TgRolloutSchedule.boost_factor must be in 1..64");
-    if (sc->reserved[0] != 0 || sc->reserved[1] != 0) return fail(TG_ERR_INVALID_ARG, "TgRolloutSchedule.reserved must be 0");
-    if ((long long)s->spcfg.rollouts * sc->boost_factor > 2147483647ll)
-        return fail(TG_ERR_INVALID_ARG, "TgSelfPlayConfig.rollouts x TgRolloutSchedule.boost_factor = " +
-                                            std::to_string((long long)s->spcfg.rollouts * sc->boost_factor) + " does not fit an int32");
-    s->sched = *sc;
-    return TG_OK;
-}
-
-int tg_selfplay_schedule_stats(TgEngine* e, uint64_t* boosted_moves, uint64_t* compact_iterations, uint64_t* compact_leaves) {
-    int rc = need_search(e);
-    if (rc) return rc;
-    Search* s = e->search;
-    if (!s->selfplay) return fail(TG_ERR_STATE, "tg_selfplay_schedule_stats: tg_selfplay_create has not been called");
-    rc = sync_and_check(e);
-    if (rc) return rc;
-    if (boosted_moves) *boosted_moves = s->boosted_moves;
-    if (compact_iterations) *compact_iterations = s->compact_iterations;
-    if (compact_leaves) *compact_leaves = s->compact_leaves;
-    return TG_OK;
-}
-
-int tg_selfplay_step(TgEngine* e, int plies) {
-    int rc = need_search(e);
-    if (rc) return rc;
-    Search* s = e->search;
-    if (!s->selfplay) return fail(TG_ERR_STATE, "tg_selfplay_create has not been called");
-    hipStream_t st = e->stream;
-    const size_t G = (size_t)s->d.G;
-    int32_t* op = s->op.as<int32_t>();
-    if (plies > 0) s->stepped = true;
-    const bool boost = s->sched.boost_plies > 0 && s->sched.boost_factor > 1;
-    for (int ply = 0; ply < plies; ply++) {
-        launch_sp_opening(st, s->d);                                   // (a) :110-116
-        launch_sp_instant_win(st, s->d, s->p);                         // (b) :119-171
-        TG_HIP(hipMemsetAsync(op, 0xFF, G * 4, st));
-        launch_sp_finish(st, s->d, s->p, op);
-        launch_reroot(st, s->d, op);
-        launch_sp_noise_mask(st, s->d, s->p);                          // (c) :174-180
-        rc = search_iterate(e, s->p.mask);
-        if (rc) return rc;
-        launch_dirichlet(st, s->d, s->p.mask, s->p.noise_alpha, s->p.noise_ratio);
-        rc = search_iterate_many(e, s->p.rollouts);                    // (d) :181-210
-        if (rc) return rc;
-        if (boost) {
-            // train/src/self_play.rs:19,63: boost_factor × rollouts while game.ply < boost_plies.  The extra iterations run over
-            // the games that are owed them only; their number sizes the grid and the network batch, hence the one wait per ply
-            launch_sp_boost_list(st, s->d, s->sched.boost_plies, s->boost_list.as<int32_t>(), s->boost_count.as<int32_t>());
-            TG_HIP(hipGetLastError());
-            TG_HIP(hipMemcpyAsync(s->h_boost_count, s->boost_count.p, 4, hipMemcpyDeviceToHost, st));
-            TG_HIP(hipStreamSynchronize(st));
-            const int count = *s->h_boost_count;
-            if (count < 0 || count > s->d.G) return fail(TG_ERR_STATE, "tg_selfplay_step: corrupt boost list");
-            const int extra = (s->sched.boost_factor - 1) * s->p.rollouts;
-            s->boosted_moves += (unsigned long long)count;
-            if (count == s->d.G) rc = search_iterate_many(e, extra);
-            else if (count > 0) {
-                rc = search_iterate_list(e, extra, count);
-                s->compact_iterations += (unsigned long long)extra;
-                s->compact_leaves += (unsigned long long)extra * (unsigned long long)count * (unsigned long long)s->d.batch;
-            }
-            if (rc) return rc;
-        }
-        launch_sp_pick(st, s->d, s->p, op);                            // (e) :212-258
-        launch_sp_finish(st, s->d, s->p, op);
-        launch_reroot(st, s->d, op);
-        launch_sp_count_ply(st, s->p);
-        TG_HIP(hipGetLastError());
-    }
-    return TG_OK;
-}
-
-int tg_selfplay_stats(TgEngine* e, TgSelfPlayStats* out) {
-    int rc = need_search(e);
-    if (rc) return rc;
-    Search* s = e->search;
-    if (!s->selfplay || !out) return fail(TG_ERR_STATE, "tg_selfplay_create has not been called");
-    rc = sync_and_check(e);
-    if (rc) return rc;
-    unsigned long long st[ST_COUNT], c[2];
-    TG_HIP(hipMemcpy(st, s->stats.p, sizeof st, hipMemcpyDeviceToHost));
-    rc = read_counters(e, &c[0], &c[1]);
-    if (rc) return rc;
-    out->games_finished = st[ST_FINISHED]; out->examples = st[ST_EXAMPLES]; out->plies = st[ST_PLIES];
-    out->white_wins = st[ST_WHITE]; out->black_wins = st[ST_BLACK]; out->draws = st[ST_DRAWS]; out->instant_wins = st[ST_INSTANT];
-    out->expansions = c[0]; out->evals = c[1];
-    out->aborted_games = st[ST_ABORTED];
-    {
-        std::vector<uint8_t> alive((size_t)s->d.G);
-        TG_HIP(hipMemcpy(alive.data(), s->alive.p, alive.size(), hipMemcpyDeviceToHost));
-        out->alive_games = 0;
-        for (uint8_t a : alive) out->alive_games += a ? 1u : 0u;
-    }
-    {   // examples the ring has overwritten since the last drain count as dropped as soon as they are observable
-        const unsigned long long ME = (unsigned long long)s->p.max_examples;
-        unsigned long long lost = st[ST_EXAMPLES] - s->drained > ME ? st[ST_EXAMPLES] - s->drained - ME : 0ull;
-        out->dropped_examples = s->dropped + lost;
-    }
-    return TG_OK;
-}
-
-int tg_selfplay_drain(TgEngine* e, int cap, TgExampleHeader* headers, void* states, TgMove* moves, uint32_t* visits, int32_t* n_out) {
-    int rc = need_search(e);
-    if (rc) return rc;
-    Search* s = e->search;
-    if (!s->selfplay) return fail(TG_ERR_STATE, "tg_selfplay_create has not been called");
-    if (cap < 0 || !n_out || (cap > 0 && (!headers || !states || !moves || !visits))) return fail(TG_ERR_INVALID_ARG, "tg_selfplay_drain: bad arguments");
-    rc = sync_and_check(e);
-    if (rc) return rc;
-    unsigned long long total = 0;
-    TG_HIP(hipMemcpy(&total, s->stats.as<unsigned long long>() + ST_EXAMPLES, 8, hipMemcpyDeviceToHost));
-    const unsigned long long ME = (unsigned long long)s->p.max_examples;
-    if (total - s->drained > ME) {  // older ones were overwritten in the ring: skipped, and counted
-        s->dropped += total - ME - s->drained;
-        s->drained = total - ME;
-    }
-    const size_t sb = (size_t)e->g.bytes;
-    const unsigned long long avail = total - s->drained;
-    const int k = (int)std::min<unsigned long long>((unsigned long long)cap, avail);
-    // the k examples are consecutive ring entries: at most two contiguous runs per array (wrap-around), one copy each
-    std::vector<ExampleRec> hdr((size_t)k);
-    for (int done = 0; done < k;) {
-        const size_t o = (size_t)((s->drained + done) % ME);
-        const int run = (int)std::min<size_t>((size_t)(k - done), (size_t)ME - o);
-        TG_HIP(hipMemcpy(hdr.data() + done, s->out_hdr.as<ExampleRec>() + o, (size_t)run * sizeof(ExampleRec), hipMemcpyDeviceToHost));
-        TG_HIP(hipMemcpy((uint8_t*)states + (size_t)done * sb, s->out_state.as<uint8_t>() + o * sb, (size_t)run * sb, hipMemcpyDeviceToHost));
-        TG_HIP(hipMemcpy(moves + (size_t)done * EX_MOVES, s->out_moves.as<uint16_t>() + o * EX_MOVES, (size_t)run * EX_MOVES * 2, hipMemcpyDeviceToHost));
-        TG_HIP(hipMemcpy(visits + (size_t)done * EX_MOVES, s->out_visits.as<uint32_t>() + o * EX_MOVES, (size_t)run * EX_MOVES * 4, hipMemcpyDeviceToHost));
-        done += run;
-    }
-    for (int i = 0; i < k; i++) {
-        headers[i].game_id = hdr[i].slot | (hdr[i].generation << 20);
-        headers[i].n_moves = hdr[i].n_moves;
-        headers[i].result = hdr[i].result;
-        headers[i].reserved = 0;
-        // entries past n_moves are whatever an earlier example left in the ring slot: clear them for the caller
-        const size_t nm = (size_t)std::min(std::max(hdr[i].n_moves, 0), (int32_t)EX_MOVES);
-        std::memset(moves + (size_t)i * EX_MOVES + nm, 0, (EX_MOVES - nm) * 2);
-        std::memset(visits + (size_t)i * EX_MOVES + nm, 0, (EX_MOVES - nm) * 4);
-    }
-    s->drained += (unsigned long long)k;
-    *n_out = k;
-    return TG_OK;
-}
-
 }  // extern "C"

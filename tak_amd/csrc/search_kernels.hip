@@ -15,6 +15,7 @@
 #include "search.cuh"
 #include "softmax.cuh"
 #include "tree_pass.cuh"
+#include "tree_launch.h"
 
 namespace tg {
 
@@ -688,20 +689,11 @@ __global__ __launch_bounds__(WPB * 64) void k_sp_pick(SearchDev S, SelfPlayDev P
 __global__ void k_sp_count_ply(SelfPlayDev P) { P.stats[ST_PLIES] += 1; }
 
 // ---- launchers --------------------------------------------------------------------------------
-static inline dim3 wgrid(int G) { return dim3((G + WPB - 1) / WPB); }
-
-// the tree kernels are compiled for the board sizes of the BASELINE configs (n as a constant) and once for any size (3×3, 4×4)
-#define TG_BY_BOARD(KERNEL, ...)                                                                          \
-    do {                                                                                                  \
-        if (S.n == 5) hipLaunchKernelGGL(KERNEL<5>, wgrid(S.G), dim3(WPB * 64), 0, st, __VA_ARGS__);      \
-        else if (S.n == 6) hipLaunchKernelGGL(KERNEL<6>, wgrid(S.G), dim3(WPB * 64), 0, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERNEL<0>, wgrid(S.G), dim3(WPB * 64), 0, st, __VA_ARGS__);               \
-    } while (0)
-void launch_select(hipStream_t st, const SearchDev& S, const uint8_t* active) { TG_BY_BOARD(k_select, S, active); }
-void launch_backup(hipStream_t st, const SearchDev& S) { TG_BY_BOARD(k_backup, S); }
+void launch_select(hipStream_t st, const SearchDev& S, const uint8_t* active) { TG_BY_BOARD(k_select, S.G, S, active); }
+void launch_backup(hipStream_t st, const SearchDev& S) { TG_BY_BOARD(k_backup, S.G, S); }
 void launch_backup_select(hipStream_t st, const SearchDev& S) {
-    if (S.batch > 1) TG_BY_BOARD(k_backup_select_batch, S);
-    else TG_BY_BOARD(k_backup_select, S);
+    if (S.batch > 1) TG_BY_BOARD(k_backup_select_batch, S.G, S);
+    else TG_BY_BOARD(k_backup_select, S.G, S);
 }
 void launch_dirichlet(hipStream_t st, const SearchDev& S, const uint8_t* active, float alpha, float ratio) {
     hipLaunchKernelGGL(k_dirichlet, dim3(S.G), dim3(64), 0, st, S, active, alpha, ratio);

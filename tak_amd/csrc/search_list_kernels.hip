@@ -4,11 +4,12 @@
 // its own: the code object of search_kernels.hip stays what it was without the schedule.
 #undef TG_TREE_STAMPS  // the stamp buffer belongs to search_kernels.hip
 #include "tree_pass.cuh"
+#include "tree_launch.h"
 
 namespace tg {
 
 // ------------------------------------------------------------------------------------------------
-// The same four kernels over a compacted list of games (the boosted iterations of a self-play ply, search.hip): wave w < count
+// The same four kernels over a compacted list of games (the boosted iterations of a self-play ply, selfplay.hip): wave w < count
 // serves game list[w], its leaves occupy slots w·batch + pass, the network is called with count × batch leaves.  Same device
 // functions, same order of operations on a game's tree as the identity-mapped kernels → same trees.  list[w] < S.G for every
 // w < count (k_sp_boost_list writes game indices only), count ≤ S.G, so every slot stays inside the G·batch per-leaf arrays.
@@ -117,20 +118,12 @@ __global__ __launch_bounds__(1024) void k_sp_boost_list(SearchDev S, int boost_p
 }
 
 // ---- launchers --------------------------------------------------------------------------------
-static inline dim3 wgrid(int G) { return dim3((G + WPB - 1) / WPB); }
-
-#define TG_BY_BOARD_LIST(KERNEL, ...)                                                                         \
-    do {                                                                                                      \
-        if (S.n == 5) hipLaunchKernelGGL(KERNEL<5>, wgrid(count), dim3(WPB * 64), 0, st, __VA_ARGS__);        \
-        else if (S.n == 6) hipLaunchKernelGGL(KERNEL<6>, wgrid(count), dim3(WPB * 64), 0, st, __VA_ARGS__);   \
-        else hipLaunchKernelGGL(KERNEL<0>, wgrid(count), dim3(WPB * 64), 0, st, __VA_ARGS__);                 \
-    } while (0)
 // over a compacted list: 0 < count ≤ S.G entries, the grid sized from count
-void launch_select_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count) { TG_BY_BOARD_LIST(k_select_list, S, list, count); }
-void launch_backup_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count) { TG_BY_BOARD_LIST(k_backup_list, S, list, count); }
+void launch_select_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count) { TG_BY_BOARD(k_select_list, count, S, list, count); }
+void launch_backup_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count) { TG_BY_BOARD(k_backup_list, count, S, list, count); }
 void launch_backup_select_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count) {
-    if (S.batch > 1) TG_BY_BOARD_LIST(k_backup_select_batch_list, S, list, count);
-    else TG_BY_BOARD_LIST(k_backup_select_list, S, list, count);
+    if (S.batch > 1) TG_BY_BOARD(k_backup_select_batch_list, count, S, list, count);
+    else TG_BY_BOARD(k_backup_select_list, count, S, list, count);
 }
 void launch_sp_boost_list(hipStream_t st, const SearchDev& S, int boost_plies, int32_t* list, int32_t* count) {
     hipLaunchKernelGGL(k_sp_boost_list, dim3(1), dim3(1024), 0, st, S, boost_plies, list, count);

@@ -11,8 +11,8 @@ is retired alone; (6) argument and state errors."""
 import numpy as np
 import pytest
 
-from test_gpu_selfplay_batch import (BLACK_FLAT, BLACK_ROAD, WHITE_FLAT, WHITE_ROAD, Replay, _assert_same_examples, _engine_examples,
-                                     _engines, _golden_net)
+from search_helpers import (BLACK_FLAT, BLACK_ROAD, WHITE_FLAT, WHITE_ROAD, Replay, _assert_same_examples, _engine_examples, _engines,
+                            _golden_net)
 
 pytestmark = pytest.mark.gpu
 

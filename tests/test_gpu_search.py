@@ -5,38 +5,9 @@ import numpy as np
 import pytest
 
 import torch_ref
+from search_helpers import _assert_same_trees, _best, _mk, _roots
 
 pytestmark = pytest.mark.gpu
-
-
-def _mk(n, evaluator, games, head=None, **kw):
-    import tak_amd
-
-    if head is None:
-        head = tak_amd.HEAD_FC5 if n == 5 else tak_amd.HEAD_CONV
-    e = tak_amd.Engine(n, evaluator=evaluator, max_batch=max(games, 64), policy_head=head, **kw)
-    return e
-
-
-def _roots(orc, n, count, seed, max_plies):
-    sts = orc.random_positions(n, count * 3, seed=seed, max_plies=max_plies, half_komi=4)
-    sts = sts[orc.result(n, sts) == 0][:count]
-    assert len(sts) == count
-    return sts
-
-
-def _assert_same_trees(e, s, games):
-    for g in range(games):
-        a, b = e.search_dump(g), s.dump(g)
-        assert len(a) == len(b), (g, len(a), len(b))
-        for f in a.dtype.names:
-            assert np.array_equal(a[f], b[f]), (g, f)
-
-
-def _best(root, g):
-    c = root["counts"][g]
-    v = root["visits"][g, :c]
-    return root["moves"][g, c - 1 - int(np.argmax(v[::-1]))]
 
 
 def test_dummynet_behaviour_3x3(orc):
@@ -295,6 +266,31 @@ def test_batched_virtual_rollouts_match_oracle(orc, n, games, batch, iters):
     e.search_run(10)
     s.run(10)
     _assert_same_trees(e, s, games)
+    e.close()
+
+
+def test_masked_and_short_runs_at_batch_4_match_oracle(orc):
+    # the iteration schedules beside the long dense one, at batch > 1: a masked run (select(mask) | evaluate | backup per iteration,
+    # nothing fused: the fused kernels take no mask), then the two ends of the fused loop — one iteration (select | backup) and
+    # two (select | backup+select | backup)
+    import tak_amd
+
+    n, games, batch = 5, 4, 4
+    e = _mk(n, tak_amd.EVAL_HASH, games * batch)
+    e.search_create(games, arena_nodes=1 << 17, batch=batch)
+    s = orc.Search(n, head=orc.HEAD_FC5, evaluator=orc.EVAL_HASH, batch=batch)
+    sts = _roots(orc, n, games, seed=12, max_plies=20)
+    e.search_reset(sts)
+    s.reset(sts)
+    mask = np.array([1, 0, 1, 1], np.uint8)
+    e.search_run(30, mask)
+    s.run(30, mask)
+    _assert_same_trees(e, s, games)
+    for iters in (1, 2):
+        e.search_run(iters)
+        s.run(iters)
+    _assert_same_trees(e, s, games)
+    assert e.search_counters() == s.counters() and s.counters()[0] > 0
     e.close()
 
 

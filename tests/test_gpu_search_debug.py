@@ -5,25 +5,11 @@ import pytest
 
 import torch_ref
 from debug_ref import assert_same, debug_ref, parse
+from search_helpers import _best, _mk, _roots
 
 pytestmark = pytest.mark.gpu
 
 SCRATCH = 1 << 26  # TG_DEBUG_SCRATCH_BYTES
-
-
-def _mk(n, evaluator, games, head=None, **kw):
-    import tak_amd
-
-    if head is None:
-        head = tak_amd.HEAD_FC5 if n == 5 else tak_amd.HEAD_CONV
-    return tak_amd.Engine(n, evaluator=evaluator, max_batch=max(games, 64), policy_head=head, **kw)
-
-
-def _roots(orc, n, count, seed, max_plies):
-    sts = orc.random_positions(n, count * 3, seed=seed, max_plies=max_plies, half_komi=4)
-    sts = sts[orc.result(n, sts) == 0][:count]
-    assert len(sts) == count
-    return sts
 
 
 def _check_against(e, dump, games, grid=((0, 0), (0, 3), (1, 3), (10, 512), (1, 512), (10, 0), (0, 512), (10, 3))):
@@ -33,12 +19,6 @@ def _check_against(e, dump, games, grid=((0, 0), (0, 3), (1, 3), (10, 512), (1, 
         assert r["cont_moves"].shape == (e.games, top_k, depth)
         for g, t in zip(games, trees):
             assert_same(r, g, debug_ref(t, depth, top_k))
-
-
-def _best(root, g):
-    c = root["counts"][g]
-    v = root["visits"][g, :c]
-    return root["moves"][g, c - 1 - int(np.argmax(v[::-1]))]
 
 
 @pytest.mark.parametrize("n,games,iters", [(5, 24, 300), (6, 12, 200), (4, 16, 300)])
