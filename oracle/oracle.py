@@ -83,6 +83,7 @@ def lib():
         l.orc_hash_eval.argtypes = [C.c_uint64]
         l.orc_philox.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         l.orc_dirichlet.argtypes = [C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        l.orc_pick_move.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
         for name in ("orc_search_free", "orc_selfplay_free"):
             getattr(l, name).argtypes = [C.c_void_p]
         _lib = l
@@ -254,6 +255,12 @@ def dirichlet(k, alpha, seed, slot, generation, ply):
     return out
 
 
+def pick_move(visits, exploitation, seed, slot, generation, ply):
+    """pick_move (tak_mcts.hpp) on a root whose children have these visit counts: the child's index, -1 without visits"""
+    visits = np.ascontiguousarray(visits, np.uint32)
+    return int(lib().orc_pick_move(len(visits), _p(visits), int(exploitation), seed, slot, generation, ply))
+
+
 def _wrap_eval(n, psize, py_eval):
     """py_eval(states[k, bytes]) -> (policy[k, P], eval[k]) wrapped as the C callback."""
     sb = state_bytes(n)
@@ -283,6 +290,10 @@ class Search:
         if getattr(self, "h", None) and lib is not None:  # (at interpreter shutdown the module's globals may be gone already)
             lib().orc_search_free(self.h)
             self.h = None
+
+    def set_threads(self, threads):
+        """OpenMP threads for the per-game phases (results are identical for any count)."""
+        lib().orc_search_threads(C.c_void_p(self.h), int(threads))
 
     def reset(self, states):
         states, k = _states(self.n, states)

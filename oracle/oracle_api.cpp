@@ -420,6 +420,13 @@ void orc_dirichlet(int k, double alpha, uint64_t seed, uint32_t slot, uint32_t g
     dirichlet_samples((size_t)k, alpha, seed, slot, generation, ply, v);
     std::memcpy(out, v.data(), (size_t)k * 4);
 }
+// pick_move on a root whose children have the given visit counts (-1: no visits to sample from)
+int orc_pick_move(int k, const uint32_t* visits, int exploitation, uint64_t seed, uint32_t slot, uint32_t generation, uint32_t ply) {
+    Node nd;
+    nd.children.resize((size_t)k);
+    for (int i = 0; i < k; i++) nd.children[i].visits = visits[i];
+    return pick_move(nd, exploitation != 0, seed, slot, generation, ply);
+}
 uint64_t orc_state_hash(int n, const uint8_t* state) { return state_hash(state, n); }
 float orc_hash_policy(uint64_t h, uint32_t i) { return hash_policy(h, i); }
 float orc_hash_eval(uint64_t h) { return hash_eval(h); }

@@ -87,6 +87,53 @@ def test_train_order_is_a_permutation_and_stable():
     assert tak_amd.train_order(1, 0).size == 0
 
 
+def test_train_order_is_the_fisher_yates_shuffle_of_rng_ref():
+    """the same permutation as the Python statement of the shuffle (tests/rng_ref.py), seeds above 2³² included: the upper half of
+    the seed is the upper half of the Philox key"""
+    import numpy as np
+
+    import rng_ref
+    import tak_amd
+
+    for seed in (7, 1 << 32, 0x9E3779B97F4A7C15, (1 << 64) - 1):
+        for n in (1, 2, 3, 1000):
+            assert tak_amd.train_order(seed, n).tolist() == rng_ref.shuffle(seed, n), (hex(seed), n)
+    assert not np.array_equal(tak_amd.train_order(0x9E3779B97F4A7C15, 1000), tak_amd.train_order(0x7F4A7C15, 1000))
+
+
+def test_train_order_is_uniform():
+    """20 000 seeds at n = 8: every position holds every value equally often, and every value lands on every position equally often.
+    Each row and each column of the position × value table is a multinomial sample of its own (the seeds are independent), so each
+    gets rng_ref's χ² gate against the uniform expectation — 16 gates of 7 degrees of freedom"""
+    import numpy as np
+
+    import rng_ref
+    import tak_amd
+
+    pytest.importorskip("scipy", reason="scipy is not installed: no chi-square survival function to gate against")
+    n, seeds = 8, 20000
+    table = np.zeros((n, n), np.int64)
+    for s in range(seeds):
+        order = tak_amd.train_order((0xC0FFEE << 32) + 977 * s, n)
+        table[np.arange(n), order] += 1
+    assert (table.sum(0) == seeds).all() and (table.sum(1) == seeds).all()
+    gates = [rng_ref.chi2_gate(f"position {i}", table[i], np.full(n, seeds / n)) for i in range(n)]
+    gates += [rng_ref.chi2_gate(f"value {v}", table[:, v], np.full(n, seeds / n)) for v in range(n)]
+    worst = min(gates, key=lambda g: g.value)
+    print(f"rng-gate train_order n=8 seeds=20000: smallest chi-square p-value {worst.value:.4g} ({worst.name}; bound {worst.bound:.0e})")
+    assert not rng_ref.failed(gates), gates
+    # teeth: the modulo-free shuffle that swaps with any position (not only those at or below i) is not uniform, and the gate sees it
+    rng = np.random.default_rng(0)
+    bad = np.zeros((n, n), np.int64)
+    for s in range(seeds):
+        order = np.arange(n)
+        for i in range(n - 1, 0, -1):
+            j = int(rng.integers(0, n))
+            order[i], order[j] = order[j], order[i]
+        bad[np.arange(n), order] += 1
+    assert rng_ref.failed([rng_ref.chi2_gate(f"position {i}", bad[i], np.full(n, seeds / n)) for i in range(n)])
+
+
 def test_sizes(lib):
     import tak_amd
 
