@@ -618,6 +618,73 @@ TG_API int tg_train_comm_info(TgEngine* e, TgCommInfo* out);
 TG_API int tg_train_comm_preflight(TgEngine* e, double* ms);
 
 /* ---------------------------------------------------------------------------------------
+ * Example window (the `examples` of training_loop, train/src/main.rs:26,56-123): one ring of `capacity` example rows in
+ * device memory, owned by the engine.  The reference keeps one Vec<Example>, extends it with every self-play round and with
+ * the `.data` files it loads (main.rs:58-80), truncates it to the latest MAX_EXAMPLES = 400_000 (main.rs:110-115) and trains
+ * a fresh copy of the network on all of it each round.  Here the examples stay where they are born and consumed: they enter
+ * from the self-play ring (tg_window_absorb) or from the host (tg_window_push) and leave as training chunks
+ * (tg_window_train) or as a host copy (tg_window_read).
+ * Logical index 0 is the oldest example kept; a new example evicts the oldest once the window is full.  Rows have the layout
+ * of tg_selfplay_drain and are canonical: moves and visits past n_moves are zero.
+ * Every entry point returns TG_ERR_INVALID_ARG for a null engine and TG_ERR_STATE for an engine without a window (before
+ * tg_window_create, or after tg_window_create(e, 0)); an engine exists only where a device does (tg_engine_create:
+ * TG_ERR_NO_DEVICE).  Host-side counters and cursors are not thread safe, as the rest of an engine.
+ * Data parallel: every rank owns the window of its own engine and fills it from its own games (or its own share of the
+ * files); nothing of a window crosses ranks, only the gradients of tg_window_train do.
+ * ------------------------------------------------------------------------------------- */
+typedef struct TgWindowInfo {
+    uint64_t capacity;  /* rows                                                                  */
+    uint64_t count;     /* examples kept: min(entered, capacity)                                 */
+    uint64_t entered;   /* examples that entered since tg_window_create / tg_window_clear        */
+    uint64_t evicted;   /* of those, no longer kept: entered - count                             */
+} TgWindowInfo; /* 32 bytes */
+/* (Re)create an empty window of `capacity` examples (main.rs:26 MAX_EXAMPLES); capacity = 0 frees it.  The window outlives
+ * tg_selfplay_create, tg_search_create, tg_train_create, tg_net_finalize, tg_train_commit and tg_pit (the loop of
+ * main.rs:82-122 recreates self-play after every pit) and dies with the engine.  capacity < 0, or a byte size beyond size_t
+ * -> TG_ERR_INVALID_ARG; a failed allocation -> TG_ERR_HIP and an engine without a window, never half of one.  Synchronises
+ * when a window is replaced. */
+TG_API int tg_window_create(TgEngine* e, int capacity);
+/* the counters above (main.rs:110-115: what the truncation has dropped is `evicted`); out = NULL -> TG_ERR_INVALID_ARG */
+TG_API int tg_window_info(TgEngine* e, TgWindowInfo* out);
+/* forget every example and zero the counters (no counterpart in main.rs:56-123: a new `examples` vector) */
+TG_API int tg_window_clear(TgEngine* e);
+/* examples.extend(new_examples) + the truncation (main.rs:106-115) without the host: every finished example of the
+ * self-play ring moves into the window on the device, in ring order — exactly the examples, in the order, that one
+ * tg_selfplay_drain with unlimited cap would return, zeros past n_moves included, game_id as drain reports it.  Shares
+ * drain's cursor: the two may be mixed on one engine and each example goes to exactly one of them; examples the ring has
+ * already overwritten are skipped and counted in TgSelfPlayStats.dropped_examples as drain counts them.  When one call
+ * brings more than `capacity` examples only the newest `capacity` are copied; the others count as entered and evicted.
+ * Synchronises once, as drain does, to learn how many there are; the copy itself is asynchronous on the engine's stream.
+ * *n_absorbed (optional) = how many entered.  Without tg_selfplay_create -> TG_ERR_STATE; device errors of the search as
+ * from tg_sync. */
+TG_API int tg_window_absorb(TgEngine* e, int32_t* n_absorbed);
+/* The same rows from the host: the `.data` files of main.rs:58-80 through tg_parse_example (layout of tg_train: states,
+ * n_moves, rows of TG_MAX_MOVES moves / visits, results; game_ids optional, NULL = 0).  Every example is checked first, as
+ * tg_train_chunk checks its own (a reachable state, 1 <= n_moves <= TG_MAX_MOVES, at least one visit): a bad one ->
+ * TG_ERR_INVALID_ARG naming its index, and the window is untouched.  Rows are made canonical on the way (whatever stands
+ * past n_moves is not copied).  n > capacity: the newest `capacity` are kept, as in tg_window_absorb.  n < 0 or a null array
+ * with n > 0 -> TG_ERR_INVALID_ARG.  Synchronises. */
+TG_API int tg_window_push(TgEngine* e, int n, const void* states, const int32_t* n_moves, const TgMove* moves,
+                          const uint32_t* visits, const float* results, const int32_t* game_ids /* NULL = 0 */);
+/* logical [first, first + n) -> host, in tg_selfplay_drain's output layout (n headers, n states, n x TG_MAX_MOVES moves and
+ * visits): what main.rs:117-121 would write to a `.data` file, or a held-out share for tg_eval_examples.  The window is not
+ * changed.  A range outside [0, count], a negative argument, or a null array with n > 0 -> TG_ERR_INVALID_ARG.
+ * Synchronises. */
+TG_API int tg_window_read(TgEngine* e, int first, int n, TgExampleHeader* headers, void* states, TgMove* moves, uint32_t* visits);
+/* Network::train (network.rs:37-56) on logical [first, first + count) of the window (main.rs:82-95 trains on all of it:
+ * first = 0, count = TgWindowInfo.count).  The result is that of tg_train(count, those examples oldest first, seed), bit for
+ * bit: losses, steps, every parameter, every BatchNorm statistic, the Adam state — the same shuffle, chunks_exact (the
+ * remainder is dropped; count < chunk_size trains nothing and returns zero losses), fresh optimiser per call, and the same
+ * two-set pipeline, with one gather kernel per chunk on the copy stream in place of the host gather and its five copies.
+ * The window is not changed.  Its examples were checked when they entered, so there is no validation pass and NO exchange
+ * of verdicts between ranks: with a communicator or a reduction hook attached every rank must pass a `count` that gives
+ * the same number of chunks (count / chunk_size), or the ranks wait for each other in an optimiser step's all-reduce —
+ * the contract callers of tg_train_chunk already have.
+ * Without tg_train_create -> TG_ERR_STATE; a range outside [0, count] or a negative argument -> TG_ERR_INVALID_ARG; after an
+ * error in the middle nothing of the trainer is left running.  Synchronises. */
+TG_API int tg_window_train(TgEngine* e, int first, int count, uint64_t seed, float* mean_loss_p, float* mean_loss_z, int32_t* steps);
+
+/* ---------------------------------------------------------------------------------------
  * Pit (replaces `pit`, train/src/pit.rs:15-96): the new network against the old one,
  * `pairs` openings × both colours, all 2·pairs games concurrently — one engine handle per weight set, each
  * holding one tree per game (the reference gives each side its own `Player`).  The side to move runs `rollouts`

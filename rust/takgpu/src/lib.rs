@@ -8,6 +8,7 @@
 //! | `Network<N>` — alpha-tak/src/model/network.rs:26-35          | [`net::GpuNet`]                        |
 //! | `Network::train` — network.rs:37-97                          | [`net::GpuNet::train`], [`dp`]         |
 //! | `self_play_parallel` — train/src/self_play.rs:96-262         | [`selfplay::self_play_parallel_gpu`]   |
+//! | `examples` of `training_loop` — train/src/main.rs:26,56-123 | [`window`]: `GpuNet::window_*`         |
 //! | `pit` — train/src/pit.rs:15-96                               | [`pit::pit_gpu`]                       |
 //! | `Game<N>` / `Move` / `Example<N>` — tak/src/game.rs:24-35, takparse, alpha-tak/src/example.rs:29-33 | [`pack`] |
 //!
@@ -18,6 +19,7 @@ pub mod net;
 pub mod pack;
 pub mod pit;
 pub mod selfplay;
+pub mod window;
 
 use std::ffi::CStr;
 

@@ -8,6 +8,12 @@ Everything runs through the C ABI (no CPU checker involved).  Prints timings of 
 size out of tg_train and prints the deployed network's losses on it (tg_eval_examples: folded BatchNorm, running statistics)
 before training and for the candidate after tg_train_commit, beside the pit line.  Under a launcher (RANK / WORLD_SIZE) every
 rank plays and holds out its own games and the sums are added over the ranks (tak_amd.dist.reduce_example_sums).
+
+--window N (default 0: the loop exactly as it is) is the training_loop of train/src/main.rs:56-123: the examples stay on the
+device.  Every round's harvest is absorbed from the self-play ring into a window of the latest N examples (tg_window_absorb) and
+the network trains on the whole window (tg_window_train), not on the fresh harvest only; nothing is drained, concatenated or
+uploaded.  With --holdout the newest share of the window is read back (tg_window_read) for tg_eval_examples and kept out by
+training on the range before it; it is trained on from the next round on, when newer examples have taken its place.
 """
 import argparse
 import json
@@ -47,13 +53,19 @@ def parse_args(argv=None):
     ap.add_argument("--pit-pairs", type=int, default=0, help="> 0: gate every round with tg_pit (train/src/main.rs:98-106)")
     ap.add_argument("--pit-rollouts", type=int, default=50, help="batches per move (pit.rs ROLLOUTS)")
     ap.add_argument("--pit-batch", type=int, default=16, help="virtual rollouts per batch (pit.rs BATCH_SIZE)")
+    ap.add_argument("--pit-arena", type=int, default=0, help="average node budget per pit game (TgPitConfig.arena_nodes); 0 = the library's "
+                    "16384, as before — --pit-rollouts x --pit-batch = 800 expansions per move exhaust that within a few moves: pass 262144")
     ap.add_argument("--holdout", type=float, default=0.0, help="> 0: harvest this fraction of --examples more, keep it out of training and "
                     "print the network's losses on it before training and after the commit (tg_eval_examples)")
     ap.add_argument("--holdout-seed", type=int, default=0, help="seed of the held-out share (round r uses [seed, r])")
     ap.add_argument("--boost-plies", type=int, default=0, help="> 0: moves below this ply get --boost-factor times the rollouts "
                     "(QUAD_ROLLOUT_PLIES, train/src/self_play.rs:19,63: 10); 0 = off")
     ap.add_argument("--boost-factor", type=int, default=1, help="rollout multiple of a boosted move (the reference: 4); 1 = off")
+    ap.add_argument("--window", type=int, default=0, help="> 0: keep the latest N examples in a window on the device and train on all of "
+                    "it every round (MAX_EXAMPLES, train/src/main.rs:26: 400000); 0 = train on the fresh harvest only")
     args = ap.parse_args(argv)
+    if args.window < 0:
+        ap.error("--window must be 0 (off) or a number of examples")
     if not 0 <= args.boost_plies <= 512:
         ap.error("--boost-plies must be in 0..512 (TG_LIMIT_GAME_PLIES)")
     if not 1 <= args.boost_factor <= 64:
@@ -62,6 +74,8 @@ def parse_args(argv=None):
         ap.error("--rollouts x --boost-factor must fit an int32")
     if not 0.0 <= args.holdout < 1.0:
         ap.error("--holdout must be in [0, 1)")
+    if args.window and args.window <= int(round(args.holdout * args.examples)):
+        ap.error("--window must hold more than the held-out share (--holdout x --examples)")
     return args
 
 
@@ -84,6 +98,8 @@ def main():
     tensors = torch_ref.abi_tensors(net)
     eng.load_state_dict(tensors)
     eng.train_create(chunk_size=args.chunk, chunks_in_step=args.chunks_in_step)
+    if args.window:
+        eng.window_create(args.window)  # outlives every selfplay_create / train_create / commit / pit below
     old = None
     if args.pit_pairs:
         old = tak_amd.Engine(args.board, res_blocks=args.blocks, filters=args.filters, evaluator=tak_amd.EVAL_RESNET,
@@ -95,26 +111,46 @@ def main():
     report = []
     for rnd in range(args.rounds):
         t0 = time.perf_counter()
-        got = [np.zeros((0,), tak_amd.engine.EXAMPLE_HEADER), np.zeros((0, eng.sb), np.uint8), np.zeros((0, 512), np.uint16), np.zeros((0, 512), np.uint32)]
-        while len(got[0]) < harvest:
-            eng.selfplay_step(4)
-            eng.sync()
-            part = eng.selfplay_drain(harvest)
-            got = [np.concatenate([a, b]) for a, b in zip(got, part)]
-        t_sp = time.perf_counter() - t0
-        hdr, states, moves, visits = [a[:harvest] for a in got]
         held_out = None
+        if args.window:
+            entered = 0
+            while entered < harvest:  # examples.extend(new_examples) + the truncation (main.rs:106-115), on the device
+                eng.selfplay_step(4)
+                entered += eng.window_absorb()
+            t_sp = time.perf_counter() - t0
+            n_train = eng.window_info()["count"] - hold  # the newest `hold` examples are the held-out share
+            if hold:
+                h_hdr, h_states, h_moves, h_visits = eng.window_read(n_train, hold)
+                held_ex = (h_states, h_hdr["n_moves"], h_moves, h_visits, h_hdr["result"])
+        else:
+            got = [np.zeros((0,), tak_amd.engine.EXAMPLE_HEADER), np.zeros((0, eng.sb), np.uint8), np.zeros((0, 512), np.uint16), np.zeros((0, 512), np.uint32)]
+            while len(got[0]) < harvest:
+                eng.selfplay_step(4)
+                eng.sync()
+                part = eng.selfplay_drain(harvest)
+                got = [np.concatenate([a, b]) for a, b in zip(got, part)]
+            t_sp = time.perf_counter() - t0
+            hdr, states, moves, visits = [a[:harvest] for a in got]
+            if hold:
+                keep, held = holdout_split(harvest, hold, [args.holdout_seed, rnd])
+                held_ex = (states[held], hdr["n_moves"][held], moves[held], visits[held], hdr["result"][held])
+                hdr, states, moves, visits = hdr[keep], states[keep], moves[keep], visits[keep]
+            n_train = len(hdr)
         if hold:
-            keep, held = holdout_split(harvest, hold, [args.holdout_seed, rnd])
-            held_ex = (states[held], hdr["n_moves"][held], moves[held], visits[held], hdr["result"][held])
-            hdr, states, moves, visits = hdr[keep], states[keep], moves[keep], visits[keep]
 
             def held_means():  # the sums of every rank's held-out examples, then the means
                 return tak_amd.engine.example_means(tdist.reduce_example_sums(group, eng.evaluate_examples(*held_ex)["sums"]))
 
             held_out = {"examples": hold * world, "before": held_means()}
         t0 = time.perf_counter()
-        lp, lz, steps = eng.train(states, hdr["n_moves"], moves, visits, hdr["result"], seed=rnd)
+        if args.window:
+            # A fresh optimiser on the whole window (main.rs:82-95).  tg_window_train exchanges no verdicts between ranks: this loop
+            # attaches no communicator, so each rank's own n_train is fine.  With one attached, the ranks' windows fill differently
+            # until they are full, and every rank must pass a count with the same count // chunk (agree on the minimum first), or
+            # the ranks wait for each other in an optimiser step's all-reduce.
+            lp, lz, steps = eng.window_train(0, n_train, seed=rnd)
+        else:
+            lp, lz, steps = eng.train(states, hdr["n_moves"], moves, visits, hdr["result"], seed=rnd)
         t_tr = time.perf_counter() - t0
         t0 = time.perf_counter()
         eng.train_commit()
@@ -124,7 +160,8 @@ def main():
         gate = None
         if old is not None:  # training_loop: keep the new network only if it beats the old one (WIN_RATE_THRESHOLD 0.55)
             t0 = time.perf_counter()
-            gate = tak_amd.pit(eng, old, pairs=args.pit_pairs, rollouts=args.pit_rollouts, batch=args.pit_batch, idle_rollouts=1, seed=rnd, max_plies=200)
+            gate = tak_amd.pit(eng, old, pairs=args.pit_pairs, rollouts=args.pit_rollouts, batch=args.pit_batch, idle_rollouts=1, seed=rnd, max_plies=200,
+                               arena_nodes=args.pit_arena)
             gate["seconds"] = time.perf_counter() - t0
             new_tensors = {k: eng.train_get_tensor(k, v.shape) for k, v in tensors.items()}
             if gate["win_rate"] > 0.55:
@@ -136,12 +173,14 @@ def main():
             gate["accepted"] = gate["win_rate"] > 0.55
             eng.selfplay_create(args.games, arena_nodes=1 << 13, seed=rnd + 1, rollouts=args.rollouts, max_examples=4 * harvest,
                                 slot_base=tdist.slot_base(rank, args.games), **schedule)
-        chunks = args.examples // args.chunk
-        report.append({"round": rnd, "selfplay_s": t_sp, "examples": int(len(hdr)), "train_s": t_tr, "chunks": chunks, "steps": steps,
+        chunks = n_train // args.chunk if args.window else args.examples // args.chunk
+        report.append({"round": rnd, "selfplay_s": t_sp, "examples": int(n_train), "train_s": t_tr, "chunks": chunks, "steps": steps,
                        "ms_per_chunk": 1e3 * t_tr / max(chunks, 1), "positions_per_s": chunks * args.chunk * 8 / t_tr,
                        "loss_p": lp, "loss_z": lz, "commit_s": t_commit, "pit": gate, "stats": eng.selfplay_stats()})
         if held_out is not None:
             report[-1]["holdout"] = held_out
+        if args.window:
+            report[-1]["window"] = eng.window_info()
         print(json.dumps(report[-1]), flush=True)
     eng.close()
     if old is not None:

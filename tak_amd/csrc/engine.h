@@ -61,6 +61,8 @@ hipError_t bind(DevBuf& b, T*& field, size_t count) {
 struct Net;     // net.hip
 struct Search;  // search_host.h
 struct Trainer; // train.hip
+struct Window;  // window.hip
+struct WindowDev;  // kernels.h
 
 }  // namespace tg
 
@@ -78,6 +80,7 @@ struct TgEngine {
     tg::Net* net = nullptr;
     tg::Search* search = nullptr;
     tg::Trainer* trainer = nullptr;
+    tg::Window* window = nullptr;  // the example window: outlives searches, self-play drivers and trainers, dies with the engine
     ~TgEngine();
 };
 
@@ -107,4 +110,11 @@ const float* net_fc_logits(const TgEngine* e, int* ld);  // FC head: logits buff
 const std::map<std::string, std::vector<float>>* net_tensors(const TgEngine* e);  // tensors as given to tg_net_set_tensor
 // train.hip
 void trainer_destroy(Trainer* t);
+// the complete host-side check of example `s` of the caller's arrays (tg_train_chunk, tg_train, tg_window_push): TG_ERR_INVALID_ARG naming it
+int validate_example(const TgEngine* e, int s, const uint8_t* states, const int32_t* n_moves, const uint32_t* visits);
+// Network::train on `count` rows of the example window, logical offset j at window row (row0 + j) % capacity (tg_window_train)
+int train_window(TgEngine* e, const WindowDev& W, uint32_t row0, int count, uint64_t seed, float* mean_loss_p, float* mean_loss_z,
+                 int32_t* steps);
+// window.hip
+void window_destroy(Window* w);
 }  // namespace tg

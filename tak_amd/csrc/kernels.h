@@ -241,4 +241,23 @@ void launch_sp_pick(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, in
 void launch_sp_boost_list(hipStream_t st, const SearchDev& S, int boost_plies, int32_t* list, int32_t* count);
 void launch_sp_count_ply(hipStream_t st, const SelfPlayDev& P);
 
+// window_kernels.hip: the example window (window.hip), a ring of `capacity` canonical example rows
+struct WindowDev {
+    uint8_t* states;     // [capacity][bytes]
+    int32_t* n_moves;    // [capacity]
+    float* result;       // [capacity]
+    int32_t* game_id;    // [capacity]
+    uint16_t* moves;     // [capacity][EX_MOVES], zero past n_moves
+    uint32_t* visits;    // [capacity][EX_MOVES], zero past n_moves
+    uint32_t capacity;   // < 2^31
+    uint32_t bytes;      // of a packed state: 256 or 384
+};
+// k examples of the self-play ring, ring rows (src0 + i) % P.max_examples, into window rows (dst0 + i) % capacity; src0 <
+// max_examples, dst0 < capacity, k ≤ min(max_examples, capacity)
+hipError_t launch_window_absorb(hipStream_t st, const SelfPlayDev& P, const WindowDev& W, uint32_t src0, uint32_t dst0, int k);
+// chunk example i < n ← window row (row0 + order[i]) % capacity into an example set of the trainer (rows of `bytes`, EX_MOVES,
+// EX_MOVES, and the 8 value targets zt[8i … 8i + 8)); row0 < capacity, 0 ≤ order[i] < capacity
+hipError_t launch_window_gather(hipStream_t st, const WindowDev& W, uint32_t row0, const int32_t* order, int n, uint8_t* states,
+                                int32_t* n_moves, uint16_t* moves, uint32_t* visits, float* zt);
+
 }  // namespace tg

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "search_host.h"
+#include "window.h"
 
 using namespace tg;
 
@@ -209,16 +210,15 @@ int tg_selfplay_drain(TgEngine* e, int cap, TgExampleHeader* headers, void* stat
     const size_t sb = (size_t)e->g.bytes;
     const unsigned long long avail = total - s->drained;
     const int k = (int)std::min<unsigned long long>((unsigned long long)cap, avail);
-    // the k examples are consecutive ring entries: at most two contiguous runs per array (wrap-around), one copy each
+    // the k examples are consecutive ring entries: at most two contiguous runs per array (wrap-around, window.h), one copy each
     std::vector<ExampleRec> hdr((size_t)k);
-    for (int done = 0; done < k;) {
-        const size_t o = (size_t)((s->drained + done) % ME);
-        const int run = (int)std::min<size_t>((size_t)(k - done), (size_t)ME - o);
-        TG_HIP(hipMemcpy(hdr.data() + done, s->p.out_hdr + o, (size_t)run * sizeof(ExampleRec), hipMemcpyDeviceToHost));
-        TG_HIP(hipMemcpy((uint8_t*)states + (size_t)done * sb, s->p.out_state + o * sb, (size_t)run * sb, hipMemcpyDeviceToHost));
-        TG_HIP(hipMemcpy(moves + (size_t)done * EX_MOVES, s->p.out_moves + o * EX_MOVES, (size_t)run * EX_MOVES * 2, hipMemcpyDeviceToHost));
-        TG_HIP(hipMemcpy(visits + (size_t)done * EX_MOVES, s->p.out_visits + o * EX_MOVES, (size_t)run * EX_MOVES * 4, hipMemcpyDeviceToHost));
-        done += run;
+    const RingRuns runs = ring_runs(s->drained, (uint64_t)k, ME);
+    for (int r = 0; r < runs.count; r++) {
+        const size_t o = (size_t)runs.start[r], done = (size_t)runs.at[r], run = (size_t)runs.len[r];
+        TG_HIP(hipMemcpy(hdr.data() + done, s->p.out_hdr + o, run * sizeof(ExampleRec), hipMemcpyDeviceToHost));
+        TG_HIP(hipMemcpy((uint8_t*)states + done * sb, s->p.out_state + o * sb, run * sb, hipMemcpyDeviceToHost));
+        TG_HIP(hipMemcpy(moves + done * EX_MOVES, s->p.out_moves + o * EX_MOVES, run * EX_MOVES * 2, hipMemcpyDeviceToHost));
+        TG_HIP(hipMemcpy(visits + done * EX_MOVES, s->p.out_visits + o * EX_MOVES, run * EX_MOVES * 4, hipMemcpyDeviceToHost));
     }
     for (int i = 0; i < k; i++) {
         headers[i].game_id = hdr[i].slot | (hdr[i].generation << 20);

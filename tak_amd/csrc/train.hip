@@ -186,13 +186,30 @@ struct Trainer {
         ar_pending[pair] = false;
     }
     DevBuf err_flag;  // one float: the ranks agree on an argument error before the first chunk of tg_train
+    // tg_window_train: the call's shuffle on the device, and the event that puts the copy stream behind the engine stream
+    DevBuf win_order;
+    hipEvent_t ev_engine = nullptr;
     ~Trainer() {
         for (auto& pair : ar_ev) for (hipEvent_t ev : pair) if (ev) (void)hipEventDestroy(ev);
+        if (ev_engine) (void)hipEventDestroy(ev_engine);
         if (comm && g_rccl.CommDestroy) g_rccl.CommDestroy(comm);
     }
 };
 
 void trainer_destroy(Trainer* t) { delete t; }
+
+// The complete host-side check of ONE example (index s of the caller's arrays), used by tg_train_chunk's upload and by
+// tg_train's pass over all examples, and by tg_window_push (engine.h declares it): a reachable state, 1 ≤ n_moves ≤ TG_MAX_MOVES, at least one visit.
+int validate_example(const TgEngine* e, int s, const uint8_t* states, const int32_t* n_moves, const uint32_t* visits) {
+    int vrc = validate_states(e, 1, states + (size_t)s * e->g.bytes, "training example");
+    if (vrc) return vrc;
+    if (n_moves[s] <= 0 || n_moves[s] > TG_MAX_MOVES)
+        return fail(TG_ERR_INVALID_ARG, "training example " + std::to_string(s) + ": n_moves out of range");
+    uint64_t total = 0;
+    for (int k = 0; k < n_moves[s]; k++) total += visits[(size_t)s * TG_MAX_MOVES + k];
+    if (total == 0) return fail(TG_ERR_INVALID_ARG, "training example " + std::to_string(s) + " without visits (the policy target would be 0/0)");
+    return TG_OK;
+}
 
 namespace {
 
@@ -518,19 +535,6 @@ void chunk_drain(Trainer* t) {
     for (Chunk::Examples& x : w.ex) x.in_flight = false;
 }
 
-// The complete host-side check of ONE example (index s of the caller's arrays), used by tg_train_chunk's upload and by
-// tg_train's pass over all examples: a reachable state, 1 ≤ n_moves ≤ TG_MAX_MOVES, at least one visit.
-int validate_example(const TgEngine* e, int s, const uint8_t* states, const int32_t* n_moves, const uint32_t* visits) {
-    int vrc = validate_states(e, 1, states + (size_t)s * e->g.bytes, "training example");
-    if (vrc) return vrc;
-    if (n_moves[s] <= 0 || n_moves[s] > TG_MAX_MOVES)
-        return fail(TG_ERR_INVALID_ARG, "training example " + std::to_string(s) + ": n_moves out of range");
-    uint64_t total = 0;
-    for (int k = 0; k < n_moves[s]; k++) total += visits[(size_t)s * TG_MAX_MOVES + k];
-    if (total == 0) return fail(TG_ERR_INVALID_ARG, "training example " + std::to_string(s) + " without visits (the policy target would be 0/0)");
-    return TG_OK;
-}
-
 // Gathers n examples (in `order`, or as they stand) into example set `slot`'s host staging and issues their five copies on the copy
 // stream; chunk_issue makes the chunk wait for them.  The set must not be in use: its previous chunk has been collected.
 // validated = the caller (tg_train) has already checked every example
@@ -576,7 +580,90 @@ void shuffle_order(uint64_t seed, int n, int* order) {
     }
 }
 
+// upload_chunk's device twin (tg_window_train): the n examples are rows of the example window, window row (row0 + order[i]) %
+// capacity for chunk example i with `order` on the device; one gather kernel on the copy stream instead of the host gather and
+// its five copies, `uploaded` recorded behind it.  Same contract: the set's previous chunk has been collected.
+int upload_chunk_window(Chunk& w, int slot, int n, const WindowDev& W, uint32_t row0, const int32_t* d_order) {
+    Chunk::Examples& x = w.ex[slot];
+    TG_HIP(launch_window_gather(w.up, W, row0, d_order, n, x.states.as<uint8_t>(), x.nmoves.as<int32_t>(), x.moves.as<uint16_t>(),
+                                x.visits.as<uint32_t>(), x.zt.as<float>()));
+    TG_HIP(hipEventRecord(x.uploaded, w.up));
+    return TG_OK;
+}
+
+// Network::train (network.rs:37-56) behind the argument checks, shared by tg_train and tg_window_train: a fresh optimiser, then
+// `total` full chunks; upload(k, slot) issues chunk k's examples into example set `slot` on the copy stream.
+template <class Upload>
+int train_chunks(TgEngine* e, int total, Upload&& upload, float* mean_loss_p, float* mean_loss_z, int32_t* steps) {
+    Trainer* t = e->trainer;
+    // a fresh optimiser per call (network.rs:40-45) on fresh gradients: the reference trains a fresh copy of the network
+    // each round (train/src/main.rs `copy`: save + load into a new VarStore), so the gradients an incomplete last step
+    // left behind (n / chunk_size not a multiple of chunks_in_step) never reach the next call's first step
+    TG_HIP(hipMemsetAsync(t->grads.p, 0, t->n_params * 4, e->stream));
+    TG_HIP(hipMemsetAsync(t->adam_m.p, 0, t->n_params * 4, e->stream));
+    TG_HIP(hipMemsetAsync(t->adam_v.p, 0, t->n_params * 4, e->stream));
+    t->adam_t = 0;
+    t->chunk_num = 0;
+    const int cs = t->cfg.chunk_size;
+    double sp = 0.0, sz = 0.0;
+    int chunks = 0, nsteps = 0;
+    Chunk& w = t->chunk;
+    // While the GPU works on chunk k the host gathers and uploads chunk k + 1 (copy stream, the other
+    // example set) and ENQUEUES it behind chunk k, then waits for chunk k's losses only (its `done` event): the chunks run one after
+    // the other on the same streams as before, with no host round trip between them.
+    int rc = TG_OK;
+    if (total > 0) {
+        rc = upload(0, 0);
+        if (rc == TG_OK) rc = chunk_issue(e, w, cs, 0);
+    }
+    for (int k = 0; k < total && rc == TG_OK; k++) {
+        if (k + 1 < total) {
+            rc = upload(k + 1, (k + 1) & 1);
+            if (rc == TG_OK) rc = chunk_issue(e, w, cs, (k + 1) & 1);
+        }
+        float lp = 0.0f, lz = 0.0f;
+        int32_t did = 0;
+        if (rc == TG_OK) rc = chunk_collect(e, w, k & 1, &lp, &lz, &did);
+        if (rc == TG_OK) { sp += lp; sz += lz; chunks++; nsteps += did; }
+    }
+    if (rc) {
+        chunk_drain(t);
+        return rc;
+    }
+    TG_HIP(hipStreamSynchronize(w.st));
+    if (mean_loss_p) *mean_loss_p = chunks ? (float)(sp / chunks) : 0.0f;
+    if (mean_loss_z) *mean_loss_z = chunks ? (float)(sz / chunks) : 0.0f;
+    if (steps) *steps = nsteps;
+    return TG_OK;
+}
+
 }  // namespace
+
+// tg_window_train behind window.hip's argument checks: Network::train on the `count` window rows (row0 + j) % capacity, j the
+// logical offset inside the trained range — the examples, the order and the chunks of tg_train(count, those rows oldest first, seed).
+int train_window(TgEngine* e, const WindowDev& W, uint32_t row0, int count, uint64_t seed, float* mean_loss_p, float* mean_loss_z,
+                 int32_t* steps) {
+    int rc = need_trainer(e);
+    if (rc) return rc;
+    Trainer* t = e->trainer;
+    Chunk& w = t->chunk;
+    std::vector<int> order((size_t)count);
+    shuffle_order(seed, count, order.data());
+    if (count > 0) {  // the permutation, once per call (nothing of an earlier call is still running: every call ends synchronised)
+        TG_HIP(t->win_order.ensure((size_t)count * 4));
+        TG_HIP(hipMemcpy(t->win_order.p, order.data(), (size_t)count * 4, hipMemcpyHostToDevice));
+    }
+    // the gathers run on the copy stream: behind whatever the engine stream still has queued (an absorb may be in flight)
+    if (!t->ev_engine) TG_HIP(hipEventCreateWithFlags(&t->ev_engine, hipEventDisableTiming));
+    TG_HIP(hipEventRecord(t->ev_engine, e->stream));
+    TG_HIP(hipStreamWaitEvent(w.up, t->ev_engine, 0));
+    const int cs = t->cfg.chunk_size;
+    const int32_t* d_order = t->win_order.as<int32_t>();
+    // chunks_exact: the remainder is dropped
+    return train_chunks(e, count / cs, [&](int k, int slot) { return upload_chunk_window(w, slot, cs, W, row0, d_order + (size_t)k * cs); },
+                        mean_loss_p, mean_loss_z, steps);
+}
+
 }  // namespace tg
 
 using namespace tg;
@@ -792,47 +879,14 @@ int tg_train(TgEngine* e, int n, const void* states, const int32_t* n_moves, con
         if (bad) return fail(TG_ERR_INVALID_ARG, local_msg);
         if (all[0] != 0.0f) return fail(TG_ERR_INVALID_ARG, "tg_train: " + std::to_string((int)all[0]) + " other rank(s) refused their examples; no rank trains");
     } else if (bad) return bad;
-    // a fresh optimiser per call (network.rs:40-45) on fresh gradients: the reference trains a fresh copy of the network
-    // each round (train/src/main.rs `copy`: save + load into a new VarStore), so the gradients an incomplete last step
-    // left behind (n / chunk_size not a multiple of chunks_in_step) never reach the next call's first step
-    TG_HIP(hipMemsetAsync(t->grads.p, 0, t->n_params * 4, e->stream));
-    TG_HIP(hipMemsetAsync(t->adam_m.p, 0, t->n_params * 4, e->stream));
-    TG_HIP(hipMemsetAsync(t->adam_v.p, 0, t->n_params * 4, e->stream));
-    t->adam_t = 0;
-    t->chunk_num = 0;
     std::vector<int> order(n);
     shuffle_order(seed, n, order.data());
     const int cs = t->cfg.chunk_size;
-    double sp = 0.0, sz = 0.0;
-    int chunks = 0, nsteps = 0;
     Chunk& w = t->chunk;
-    // chunks_exact: the remainder is dropped.  While the GPU works on chunk k the host gathers and uploads chunk k + 1 (copy stream, the other
-    // example set) and ENQUEUES it behind chunk k, then waits for chunk k's losses only (its `done` event): the chunks run one after
-    // the other on the same streams as before, with no host round trip between them.
-    const int total = n / cs;
-    if (total > 0) {
-        rc = upload_chunk(e, w, 0, cs, (const uint8_t*)states, n_moves, moves, visits, results, order.data(), true);
-        if (rc == TG_OK) rc = chunk_issue(e, w, cs, 0);
-    }
-    for (int k = 0; k < total && rc == TG_OK; k++) {
-        if (k + 1 < total) {
-            rc = upload_chunk(e, w, (k + 1) & 1, cs, (const uint8_t*)states, n_moves, moves, visits, results, order.data() + (size_t)(k + 1) * cs, true);
-            if (rc == TG_OK) rc = chunk_issue(e, w, cs, (k + 1) & 1);
-        }
-        float lp = 0.0f, lz = 0.0f;
-        int32_t did = 0;
-        if (rc == TG_OK) rc = chunk_collect(e, w, k & 1, &lp, &lz, &did);
-        if (rc == TG_OK) { sp += lp; sz += lz; chunks++; nsteps += did; }
-    }
-    if (rc) {
-        chunk_drain(t);
-        return rc;
-    }
-    TG_HIP(hipStreamSynchronize(w.st));
-    if (mean_loss_p) *mean_loss_p = chunks ? (float)(sp / chunks) : 0.0f;
-    if (mean_loss_z) *mean_loss_z = chunks ? (float)(sz / chunks) : 0.0f;
-    if (steps) *steps = nsteps;
-    return TG_OK;
+    // chunks_exact: the remainder is dropped
+    return train_chunks(e, n / cs, [&](int k, int slot) {
+        return upload_chunk(e, w, slot, cs, (const uint8_t*)states, n_moves, moves, visits, results, order.data() + (size_t)k * cs, true);
+    }, mean_loss_p, mean_loss_z, steps);
 }
 
 int tg_train_order(uint64_t seed, int n, int32_t* order) {

@@ -56,6 +56,13 @@ class TgRolloutSchedule(C.Structure):
     _fields_ = [("boost_plies", C.c_int32), ("boost_factor", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class TgWindowInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("capacity", "count", "entered", "evicted")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class TgSelfPlayStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in (
         "games_finished", "examples", "expansions", "evals", "plies", "white_wins", "black_wins", "draws", "instant_wins",
@@ -135,6 +142,7 @@ ABI_SYMBOLS = [
     "tg_search_root", "tg_search_play", "tg_search_states", "tg_search_dump", "tg_search_debug", "tg_search_counters", "tg_search_pool",
     "tg_selfplay_create", "tg_selfplay_step", "tg_selfplay_stats", "tg_selfplay_drain",
     "tg_selfplay_set_schedule", "tg_selfplay_schedule_stats",
+    "tg_window_create", "tg_window_info", "tg_window_clear", "tg_window_absorb", "tg_window_push", "tg_window_read", "tg_window_train",
     "tg_profile_enable", "tg_profile_read", "tg_board_pass_bench",
     "tg_augment_examples", "tg_eval_examples",
     "tg_train_create", "tg_train_chunk", "tg_train", "tg_train_step", "tg_train_forward", "tg_train_get_tensor",
@@ -774,9 +782,13 @@ class Engine:
         self._check(self.lib.tg_selfplay_stats(self.h, C.byref(s)))
         return s.as_dict()
 
-    def write_examples(self, path, cap=1 << 16):
-        """Drain finished examples and append them to `path` in the reference's `.data` text format."""
-        hdr, states, moves, visits = self.selfplay_drain(cap)
+    def write_examples(self, path, cap=1 << 16, window=None):
+        """Drain finished examples and append them to `path` in the reference's `.data` text format.
+        window=(first, n): write that logical range of the example window instead (window_read; nothing is drained or removed)."""
+        if window is not None:
+            hdr, states, moves, visits = self.window_read(*window)
+        else:
+            hdr, states, moves, visits = self.selfplay_drain(cap)
         with open(path, "a") as f:
             for i in range(len(hdr)):
                 k = int(hdr["n_moves"][i])
@@ -792,3 +804,48 @@ class Engine:
         self._check(self.lib.tg_selfplay_drain(self.h, cap, _p(hdr), _p(states), _p(moves), _p(visits), C.byref(k)))
         k = k.value
         return hdr[:k].copy(), states[:k].copy(), moves[:k].copy(), visits[:k].copy()
+
+    # ---- the example window of training_loop (train/src/main.rs:26,56-123) on the device -----------
+    def window_create(self, capacity):
+        """(re)create an empty window of `capacity` examples; 0 frees it.  It outlives selfplay_create, train_create, commits and pits"""
+        self._check(self.lib.tg_window_create(self.h, int(capacity)))
+
+    def window_info(self):
+        """{capacity, count, entered, evicted}: count = min(entered, capacity), counted since window_create / window_clear"""
+        info = TgWindowInfo()
+        self._check(self.lib.tg_window_info(self.h, C.byref(info)))
+        return info.as_dict()
+
+    def window_clear(self):
+        self._check(self.lib.tg_window_clear(self.h))
+
+    def window_absorb(self):
+        """every finished example of the self-play ring -> the window, on the device, in drain's order (shares drain's cursor)
+        -> how many entered"""
+        k = C.c_int32(0)
+        self._check(self.lib.tg_window_absorb(self.h, C.byref(k)))
+        return k.value
+
+    def window_push(self, states, n_moves, moves, visits, results, game_ids=None):
+        """the same rows from the host (read_examples' layout); every example is validated first, a bad one raises and
+        leaves the window untouched"""
+        states, k, n_moves, moves, visits, results = self._examples(states, n_moves, moves, visits, results)
+        ids = np.ascontiguousarray(game_ids, np.int32).reshape(k) if game_ids is not None else None
+        self._check(self.lib.tg_window_push(self.h, k, _p(states), _p(n_moves), _p(moves), _p(visits), _p(results), _p(ids)))
+
+    def window_read(self, first, n):
+        """logical [first, first + n) of the window (0 = oldest) in selfplay_drain's layout -> (headers, states, moves, visits)"""
+        rows = max(int(n), 0)
+        hdr = np.zeros(rows, EXAMPLE_HEADER)
+        states = np.zeros((rows, self.sb), np.uint8)
+        moves = np.zeros((rows, TG_MAX_MOVES), np.uint16)
+        visits = np.zeros((rows, TG_MAX_MOVES), np.uint32)
+        self._check(self.lib.tg_window_read(self.h, int(first), int(n), _p(hdr), _p(states), _p(moves), _p(visits)))
+        return hdr, states, moves, visits
+
+    def window_train(self, first, count, seed=0):
+        """Network::train on logical [first, first + count) of the window: bit for bit train() on those examples, oldest first
+        -> (mean loss_p, mean loss_z, optimiser steps)"""
+        lp, lz, steps = C.c_float(0), C.c_float(0), C.c_int32(0)
+        self._check(self.lib.tg_window_train(self.h, int(first), int(count), C.c_uint64(seed), C.byref(lp), C.byref(lz), C.byref(steps)))
+        return lp.value, lz.value, steps.value
