@@ -283,6 +283,27 @@ TG_API int tg_forward_mcts(TgEngine* e, int n, const float* planes, float* polic
  * pointers; no synchronisation. */
 TG_API int tg_policy_eval_dev(TgEngine* e, int n, const void* d_states, float* d_policy, float* d_eval);
 
+/* Symmetry ensemble of tg_policy_eval: the mean of the network's output over chosen dihedral images of every state, mapped
+ * back to the state's own orientation.  No counterpart in the reference, which uses the symmetries of tak/src/symm.rs:11-20
+ * for training examples only (alpha-tak/src/example.rs:62-78); this is the same group, in the same order, at the evaluation.
+ *   mask: bit s set = image s (tg_augment_examples' order, s = 0 the identity) takes part; 0xFF = the whole group.  mask = 0
+ *     or a bit above 7 → TG_ERR_INVALID_ARG.  The engine must use TG_EVAL_RESNET with finalized weights, else TG_ERR_STATE.
+ *     n = 0 returns TG_OK.
+ *   With k = popcount(mask), p_s / v_s = what tg_policy_eval returns for image s of state i (in tg_net_set_precision's
+ *   arithmetic), and perm[s][j] = the policy slot of the image under s of the move whose slot is j (tables built on the device
+ *   at tg_net_finalize from the move transform and move index of tg_augment_examples):
+ *       policy[i][j] = (Σ_s p_s[i][perm[s][j]]) · (1/k)        eval[i] = (Σ_s v_s[i]) · (1/k)
+ *   ORDER: both sums run in f32 over ASCENDING s, starting from the first selected image (no zero is added in front of it);
+ *   the product with the f32 constant 1.0f / (float)k comes last.  So mask = 1 << s is tg_policy_eval of image s de-permuted,
+ *   and mask = 0x01 is tg_policy_eval bit for bit.  A state's outputs do not depend on the other states of the call.
+ *   The host variant slices by ⌊max_batch / k⌋ states itself and synchronises (max_batch < k → TG_ERR_INVALID_ARG); the _dev
+ *   variant takes device pointers, requires n · k ≤ max_batch and does not synchronise, like tg_policy_eval_dev. */
+TG_API int tg_policy_eval_symm(TgEngine* e, int n, const void* states, uint32_t mask, float* policy, float* eval);
+TG_API int tg_policy_eval_symm_dev(TgEngine* e, int n, const void* d_states, uint32_t mask, float* d_policy, float* d_eval);
+/* The device's permutation tables as tg_net_finalize built them: 8 × P int32, perm[s·P + j] (−1 = slot j has no image; none is
+ * expected).  No counterpart in the reference (tak/src/symm.rs:11-20 is the group).  Diagnostic read for tests; synchronises. */
+TG_API int tg_symm_perm_read(TgEngine* e, int32_t* perm);
+
 /* ---------------------------------------------------------------------------------------
  * Search (replaces Node + Node::{virtual_rollout, devirtualize_path, select, apply_dirichlet,
  * pick_move, play}, alpha-tak/src/search/{node,mcts,noise,play}.rs) for `games` independent
@@ -325,6 +346,25 @@ TG_API int tg_search_reset(TgEngine* e, const void* states);
 /* run `iters` lock-step iterations (virtual_rollout → policy_eval → devirtualize_path).
  * active: optional host mask (games bytes, 0 = skip this game), NULL = all. */
 TG_API int tg_search_run(TgEngine* e, int iters, const uint8_t* active);
+/* One pseudo-random dihedral image per evaluated leaf (AlphaGo Zero's scheme).  No counterpart in the reference, whose search
+ * shows the network every position in the orientation it arose in; the group and its order are tak/src/symm.rs:11-20.
+ *   TG_SYMM_HASHED: a leaf that goes to the network goes there as its image under
+ *       s = philox4x32_10(TgSearchConfig.seed; hash_lo, hash_hi, 0x73796d6d, 0)[0] & 7,
+ *     hash = the 64-bit hash of the leaf's packed state (the one TG_EVAL_HASH evaluates), and its children's priors come back
+ *     through the inverse permutation (tg_policy_eval_symm's tables).  s depends on the position and the seed only — not on the
+ *     slot, the iteration or the batch pass — so transpositions agree and a sharded run equals the full run.  The value needs
+ *     no mapping.
+ *   Set it after tg_search_create / tg_selfplay_create and before the next iteration runs; it is sticky for that search object —
+ *   tg_search_run and tg_selfplay_step (dense and compacted iterations, any batch) — and the next tg_search_create /
+ *   tg_selfplay_create resets it to TG_SYMM_OFF.  tg_pit creates its own searches: it takes over the mode each of its two
+ *   engines holds when it is called (set it on each engine before the call; an engine without a search keeps the mode for that
+ *   purpose).  Requires TG_EVAL_RESNET (else TG_ERR_STATE); an unknown mode → TG_ERR_INVALID_ARG.  TG_SYMM_OFF (the default)
+ *   launches nothing and changes nothing.
+ *   tg_search_get_symmetry: the mode, and the engine's count of leaves sent to the network under s ≠ 0 since the engine was
+ *   created (synchronises). */
+typedef enum TgSearchSymmetry { TG_SYMM_OFF = 0, TG_SYMM_HASHED = 1 } TgSearchSymmetry;
+TG_API int tg_search_set_symmetry(TgEngine* e, int mode);
+TG_API int tg_search_get_symmetry(TgEngine* e, int* mode, uint64_t* leaves_transformed);
 /* Node::apply_dirichlet (noise.rs:6-16) on every active root with engine RNG
  * (stream = (seed, game, ply)). */
 TG_API int tg_search_apply_dirichlet(TgEngine* e, float alpha, float ratio, const uint8_t* active);

@@ -165,6 +165,26 @@ impl<const N: usize> GpuNet<N> {
         Ok((lp, lz, steps))
     }
 
+    /// The symmetry ensemble of `policy_eval` (tg_policy_eval_symm): the mean of the network's output over the dihedral images that
+    /// `mask` selects (bit s = image s in the order of tak/src/symm.rs:11-20, 0xFF = all eight), mapped back to each game's own
+    /// orientation.  The reference has no counterpart; `mask = 0x01` is `policy_eval` bit for bit.
+    pub fn policy_eval_symm(&self, games: &[Game<N>], mask: u32) -> Result<Vec<(Vec<f32>, f32)>, crate::TgError> {
+        if games.is_empty() {
+            return Ok(Vec::new());
+        }
+        let sb = pack::state_bytes(N);
+        let mut states = vec![0u8; sb * games.len()];
+        for (g, chunk) in games.iter().zip(states.chunks_mut(sb)) {
+            pack::pack_game(g, chunk);
+        }
+        let mut policy = vec![0f32; self.policy_len * games.len()];
+        let mut eval = vec![0f32; games.len()];
+        check(unsafe {
+            sys::tg_policy_eval_symm(self.e, games.len() as i32, states.as_ptr() as *const _, mask, policy.as_mut_ptr(), eval.as_mut_ptr())
+        })?;
+        Ok(policy.chunks(self.policy_len).map(<[f32]>::to_vec).zip(eval).collect())
+    }
+
     /// Losses of the deployed network — folded BatchNorm, running statistics: what `policy_eval`, self-play and the pit run — on
     /// examples it may never have seen (tg_eval_examples; the reference prints network.rs:86's training losses only).  Returns the
     /// SUMS over positions (`examples.len()`, or 8 × that with `symmetries`), which add over calls and ranks: means are

@@ -16,6 +16,7 @@ pub struct SelfPlaySettings {
     pub batch: i32,         // virtual rollouts per game and iteration (Player's batching, BATCH_SIZE 32 in the reference's self_play); 1 = one leaf per game
     pub boost_plies: i32,   // QUAD_ROLLOUT_PLIES (10 in the reference's self_play): moves below this ply get boost_factor × rollouts; 0 = off
     pub boost_factor: i32,  // 4 in the reference's self_play; 1 = off
+    pub symmetry: i32,      // sys::TG_SYMM_HASHED: every evaluated leaf goes to the network as a hashed dihedral image (no counterpart in the reference); TG_SYMM_OFF = off
     pub noise_alpha: f32,
     pub noise_ratio: f32,
     pub noise_plies: i32,
@@ -36,6 +37,7 @@ impl Default for SelfPlaySettings {
             batch: 1,
             boost_plies: 0,
             boost_factor: 1,
+            symmetry: sys::TG_SYMM_OFF,
             noise_alpha: 0.2,
             noise_ratio: 0.3,
             noise_plies: 80,
@@ -107,6 +109,9 @@ pub fn self_play_with_report<const N: usize>(network: &GpuNet<N>, s: SelfPlaySet
         // train/src/self_play.rs:19,63; with it tg_selfplay_step waits once per ply (takgpu.h)
         let schedule = sys::TgRolloutSchedule { boost_plies: s.boost_plies, boost_factor: s.boost_factor, reserved: [0, 0] };
         check(unsafe { sys::tg_selfplay_set_schedule(network.e, &schedule) })?;
+    }
+    if s.symmetry != sys::TG_SYMM_OFF {
+        check(unsafe { sys::tg_search_set_symmetry(network.e, s.symmetry) })?;
     }
     let mut file = s.example_dir.map(|d| File::create(format!("{d}/{}.data", sys_time())).unwrap()); // self_play.rs:98
     let sb = pack::state_bytes(N);

@@ -61,6 +61,9 @@ def parse_args(argv=None):
     ap.add_argument("--boost-plies", type=int, default=0, help="> 0: moves below this ply get --boost-factor times the rollouts "
                     "(QUAD_ROLLOUT_PLIES, train/src/self_play.rs:19,63: 10); 0 = off")
     ap.add_argument("--boost-factor", type=int, default=1, help="rollout multiple of a boosted move (the reference: 4); 1 = off")
+    ap.add_argument("--symmetry", choices=("off", "hashed"), default="off", help="hashed: self-play and the pit send every leaf to the "
+                    "network as a pseudo-random dihedral image (tg_search_set_symmetry); with --holdout the report also carries the "
+                    "network's distance from equivariance")
     ap.add_argument("--window", type=int, default=0, help="> 0: keep the latest N examples in a window on the device and train on all of "
                     "it every round (MAX_EXAMPLES, train/src/main.rs:26: 400000); 0 = train on the fresh harvest only")
     args = ap.parse_args(argv)
@@ -105,7 +108,7 @@ def main():
         old = tak_amd.Engine(args.board, res_blocks=args.blocks, filters=args.filters, evaluator=tak_amd.EVAL_RESNET,
                              max_batch=2 * args.pit_pairs * args.pit_batch)
         old.load_state_dict(tensors)
-    schedule = dict(boost_plies=args.boost_plies, boost_factor=args.boost_factor)
+    schedule = dict(boost_plies=args.boost_plies, boost_factor=args.boost_factor, symmetry=args.symmetry)
     eng.selfplay_create(args.games, arena_nodes=1 << 13, seed=0, rollouts=args.rollouts, max_examples=4 * harvest,
                         slot_base=tdist.slot_base(rank, args.games), **schedule)
     report = []
@@ -141,7 +144,14 @@ def main():
             def held_means():  # the sums of every rank's held-out examples, then the means
                 return tak_amd.engine.example_means(tdist.reduce_example_sums(group, eng.evaluate_examples(*held_ex)["sums"]))
 
-            held_out = {"examples": hold * world, "before": held_means()}
+            def equivariance():  # mean |p − p̄| and |v − v̄| between the plain and the 8-image ensembled evaluation, over every rank's share
+                p, v = eng.policy_eval(held_ex[0])
+                pe, ve = eng.policy_eval(held_ex[0], symmetries=0xFF)
+                mine = [float(np.abs(p - pe).sum(dtype=np.float64)), float(p.size), float(np.abs(v - ve).sum(dtype=np.float64)), float(v.size)]
+                dp, n_p, dv, n_v = (sum(col) for col in zip(*tdist.gather(group, mine)))  # the ranks' sums in f64, then the means
+                return {"mean_abs_dp": dp / n_p if n_p else None, "mean_abs_dv": dv / n_v if n_v else None}
+
+            held_out = {"examples": hold * world, "before": held_means(), "equivariance_before": equivariance()}
         t0 = time.perf_counter()
         if args.window:
             # A fresh optimiser on the whole window (main.rs:82-95).  tg_window_train exchanges no verdicts between ranks: this loop
@@ -157,11 +167,12 @@ def main():
         t_commit = time.perf_counter() - t0
         if held_out is not None:  # the candidate, as the pit is about to play it
             held_out["after"] = held_means()
+            held_out["equivariance_after"] = equivariance()
         gate = None
         if old is not None:  # training_loop: keep the new network only if it beats the old one (WIN_RATE_THRESHOLD 0.55)
             t0 = time.perf_counter()
             gate = tak_amd.pit(eng, old, pairs=args.pit_pairs, rollouts=args.pit_rollouts, batch=args.pit_batch, idle_rollouts=1, seed=rnd, max_plies=200,
-                               arena_nodes=args.pit_arena)
+                               arena_nodes=args.pit_arena, symmetry=args.symmetry)
             gate["seconds"] = time.perf_counter() - t0
             new_tensors = {k: eng.train_get_tensor(k, v.shape) for k, v in tensors.items()}
             if gate["win_rate"] > 0.55:

@@ -230,6 +230,13 @@ class Analysis:
         return "".join(out)
 
 
+def root_eval(engine, states, ensemble=True):
+    """The network's own view of root positions, for analysis: (policy [k, P], eval [k]).  ensemble = True evaluates every root with
+    the full symmetry ensemble (Engine.policy_eval(symmetries=0xFF): the mean over the 8 dihedral images mapped back to the root's
+    orientation) — a quieter evaluation than the single orientation the search sees; False is the plain Network::policy_eval."""
+    return engine.policy_eval(states, symmetries=0xFF if ensemble else None)
+
+
 def _format_branch(ply, info):
     """analysis.rs:194-232: `{ply_move}`, the candidate with its comment, then its continuation moves with more than
     BRANCH_MIN_VISITS visits, two plies a line"""

@@ -2,6 +2,7 @@
 // Kernels behind tg_movegen / tg_play / tg_result / tg_encode / tg_move_index / tg_perft.
 #include "board.cuh"
 #include "kernels.h"
+#include "symm.cuh"
 
 namespace tg {
 
@@ -142,7 +143,8 @@ __global__ __launch_bounds__(256) void k_augment(const uint8_t* __restrict__ sta
     Geom g = make_geom(n);
     WState s;
     ws_load(s, states + (size_t)ex * g.bytes, g);
-    // board: the square this lane ends up holding comes from its pre-image under the symmetry
+    // board: the square this lane ends up holding comes from its pre-image under the symmetry (symm.cuh ws_symm_image is
+    // these lines; calling it here reorders two instructions of this kernel, which is kept as it was)
     int col = lane % n, row = lane / n;
     sym_apply_inverse(n, sym, col, row);
     int src = lane < g.nsq ? row * n + col : lane;
@@ -161,12 +163,7 @@ __global__ __launch_bounds__(256) void k_augment(const uint8_t* __restrict__ sta
     const float total = (float)part;
     float* row_pi = pi + (size_t)wi * P;
     for (int k = lane; k < nm; k += 64) {
-        uint32_t m = mv[k];
-        int c = (int)(m & 63u) % n, r = (int)(m & 63u) / n;
-        sym_apply(n, sym, c, r);
-        uint32_t pat = m >> 8, f = (m >> 6) & 3u;
-        if (pat) f = sym_dir(sym, f);
-        uint32_t tm = (uint32_t)(r * n + c) | (f << 6) | (pat << 8);
+        uint32_t tm = move_symm_image(mv[k], n, sym);
         int idx = move_index_dev(tm, n, legacy5 != 0, lut5);
         if (idx >= 0 && idx < P) row_pi[idx] = (float)vs[k] / total;
     }

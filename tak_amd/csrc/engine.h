@@ -63,6 +63,7 @@ struct Search;  // search_host.h
 struct Trainer; // train.hip
 struct Window;  // window.hip
 struct WindowDev;  // kernels.h
+struct SearchDev;  // search.cuh
 
 }  // namespace tg
 
@@ -81,6 +82,10 @@ struct TgEngine {
     tg::Search* search = nullptr;
     tg::Trainer* trainer = nullptr;
     tg::Window* window = nullptr;  // the example window: outlives searches, self-play drivers and trainers, dies with the engine
+    // dihedral symmetries (symm.hip): the policy permutation tables int32[8][P] built at tg_net_finalize, tg_policy_eval_symm's
+    // staging (the caller's states; the folded outputs), the search's mode (TgSearchSymmetry) and its count of transformed leaves
+    tg::DevBuf symm_perm, symm_src, symm_policy, symm_eval, symm_count;
+    int symm_mode = 0;
     ~TgEngine();
 };
 
@@ -117,4 +122,9 @@ int train_window(TgEngine* e, const WindowDev& W, uint32_t row0, int count, uint
                  int32_t* steps);
 // window.hip
 void window_destroy(Window* w);
+// symm.hip
+int symm_tables_build(TgEngine* e);  // (tg_net_finalize) the device tables behind tg_policy_eval_symm and TG_SYMM_HASHED, built once
+// (search_iterate) the hashed image of the iteration's leaves, between the tree kernel and the forward; TG_SYMM_OFF: nothing
+int symm_search_leaves(TgEngine* e, const SearchDev& d, int leaves);
+int symm_search_prepare(TgEngine* e);  // the engine's mode onto its search: a search fed by planes is fed by packed leaf states instead
 }  // namespace tg

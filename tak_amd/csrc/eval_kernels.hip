@@ -8,6 +8,7 @@
 #include "board.cuh"
 #include "kernels.h"
 #include "softmax.cuh"
+#include "symm.cuh"
 
 namespace tg {
 
@@ -31,6 +32,7 @@ __global__ __launch_bounds__(256) void k_eval_images(const uint8_t* __restrict__
     const Geom g = make_geom(n);
     WState s;
     ws_load(s, states + (size_t)ex * g.bytes, g);
+    // (symm.cuh ws_symm_image is these lines; calling it here reorders two instructions of this kernel, which is kept as it was)
     int col = lane % n, row = lane / n;
     sym_apply_inverse(n, sym, col, row);
     const int src = lane < g.nsq ? row * n + col : lane;
@@ -107,12 +109,7 @@ __global__ __launch_bounds__(256) void k_example_metrics(const float* __restrict
     float best_l = -INFINITY;
     int best_lk = -1;
     for (int k = lane; k < nm; k += 64) {
-        const uint32_t m = mv[k];
-        int c = (int)(m & 63u) % n, r = (int)(m & 63u) / n;
-        sym_apply(n, sym, c, r);
-        uint32_t pat = m >> 8, f = (m >> 6) & 3u;
-        if (pat) f = sym_dir(sym, f);
-        const uint32_t tm = (uint32_t)(r * n + c) | (f << 6) | (pat << 8);
+        const uint32_t tm = move_symm_image(mv[k], n, sym);
         const int idx = move_index_dev(tm, n, legacy5 != 0, lut5);
         const bool ok = idx >= 0 && idx < R * C;
         const float l = ok ? x[(size_t)(idx % R) * cs + idx / R] : -INFINITY;

@@ -241,6 +241,18 @@ void launch_sp_pick(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, in
 void launch_sp_boost_list(hipStream_t st, const SearchDev& S, int boost_plies, int32_t* list, int32_t* count);
 void launch_sp_count_ply(hipStream_t st, const SelfPlayDev& P);
 
+// symm_kernels.hip: the dihedral symmetries at the evaluation (tg_policy_eval_symm) and in the search (TG_SYMM_HASHED)
+// perm[8][P]: perm[s][j] = policy slot of the image under s of the move whose slot is j; the caller fills it with −1 first
+hipError_t launch_symm_perm(hipStream_t st, int n, int P, bool legacy5, const int16_t* lut5, int32_t* perm);
+// the k = popcount(mask) selected images of `count` states, image r of state i at row i·k + r of `out`
+hipError_t launch_symm_images(hipStream_t st, const uint8_t* states, int count, int k, uint32_t mask, int n, uint8_t* out);
+// policy[i][j] = (Σ_s p[i·k + r(s)][perm[s][j]]) · (1/k), eval[i] = (Σ_s v[i·k + r(s)]) · (1/k): f32, ascending s, product last
+hipError_t launch_symm_fold(hipStream_t st, const float* p, const float* v, const int32_t* perm, int count, int P, int k, uint32_t mask,
+                            float* policy, float* eval);
+// between the tree kernel and the forward: every slot < leaves with leaf_kind 1 gets its leaf_state replaced by the image under
+// the hashed s (rng.cuh RNG_SYMM_TAG) and its child_pidx mapped through perm[s]; *transformed counts the slots with s ≠ 0
+hipError_t launch_symm_leaves(hipStream_t st, const SearchDev& S, int leaves, const int32_t* perm, unsigned long long* transformed);
+
 // window_kernels.hip: the example window (window.hip), a ring of `capacity` canonical example rows
 struct WindowDev {
     uint8_t* states;     // [capacity][bytes]

@@ -531,6 +531,7 @@ int net_finalize(TgEngine* e) {
     n->fc_stat_blocks = n->fc_stats_on ? FC_STAT_BLOCKS : 0;
     n->fc_stat_stride = n->fc_stats_on ? FC_STAT_STRIDE : 0;
     if (n->fc_stats_on) TG_HIP(n->fc_stats.ensure(mb * (size_t)n->fc_stat_stride * 2 * 4));
+    if (int rc = symm_tables_build(e); rc) return rc;  // once per engine: the policy permutation tables of the 8 symmetries
     n->ready = true;
     return TG_OK;
 }

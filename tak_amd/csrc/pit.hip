@@ -88,8 +88,13 @@ extern "C" int tg_pit(TgEngine* e_new, TgEngine* e_old, const TgPitConfig* cfg, 
     sc.batch = (uint32_t)batch;
     TgEngine* eng[2] = {e_new, e_old};
     for (TgEngine* e : eng) {
+        const int symmetry = e->symm_mode;  // tg_search_set_symmetry before the call: the create resets it, this match keeps it
         rc = tg_search_create(e, &sc);
         if (rc) return rc;
+        if (symmetry != TG_SYMM_OFF) {
+            rc = tg_search_set_symmetry(e, symmetry);
+            if (rc) return rc;
+        }
         rc = tg_search_reset(e, states.data());
         if (rc) return rc;
     }

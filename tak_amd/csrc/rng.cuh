@@ -13,6 +13,11 @@
 namespace tg {
 
 enum : uint32_t { RNG_OPENING = 1, RNG_GAMMA = 2, RNG_PICK = 3 };
+// The hashed leaf image of the search (TG_SYMM_HASHED, symm_kernels.hip) is keyed by the POSITION, not by (slot, generation, ply):
+//   s = philox4x32_10(seed; hash_lo, hash_hi, RNG_SYMM_TAG, 0).v[0] & 7,   hash = ws_hash of the leaf's packed state.
+// Its counter domain is apart from every other use: rng_draw's third word is ply | purpose << 16 with purpose ≤ 9 (the three
+// above, tg_pit's 8 and 9), so < 0x000A0000; tg_net_init_random's fourth word is 0x696e6974, this one's is 0.
+constexpr uint32_t RNG_SYMM_TAG = 0x73796d6du;  // "symm"
 
 struct U4 { uint32_t v[4]; };
 

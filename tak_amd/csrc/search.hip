@@ -96,6 +96,7 @@ int search_alloc(TgEngine* e, const TgSearchConfig* cfg, size_t tree_growth) {
         search_destroy(e->search);
         e->search = nullptr;
     }
+    e->symm_mode = TG_SYMM_OFF;  // tg_search_set_symmetry is sticky for ONE search object
     std::unique_ptr<Search> sp(new Search());
     Search* s = sp.get();
     s->cfg = *cfg;
@@ -258,6 +259,7 @@ struct GatherScope {
 //   otherwise:       select(0) | net | backup(0)+select(1) | net | … | backup(iters-1): one tree kernel per iteration
 //   list given:      the same over the compacted list of `count` games (0 < count < G): wave w serves list[w], leaf slots
 //                    w·batch + pass, the network on count × batch leaves
+//   TG_SYMM_HASHED:  one more kernel in front of every `net` (k_symm_leaves over the iteration's leaf slots); off: none
 int search_iterate(TgEngine* e, int iters, const uint8_t* d_active, const int32_t* list, int count) {
     Search* s = e->search;
     if (iters <= 0 || (list && count <= 0)) return TG_OK;
@@ -267,12 +269,19 @@ int search_iterate(TgEngine* e, int iters, const uint8_t* d_active, const int32_
     SearchDev d = s->d;
     d.pass = d.batch > 1 ? -1 : 0;  // -1: the kernel runs the `batch` passes of a game back to back in that game's wave
     hipStream_t st = e->stream;
+    // TG_SYMM_HASHED: every evaluated leaf goes to the network as its hashed dihedral image (symm.hip), from packed leaf states
+    const bool symm = e->symm_mode == TG_SYMM_HASHED && e->cfg.evaluator == TG_EVAL_RESNET;
+    if (symm) {
+        if (int rc = symm_search_prepare(e); rc) return rc;
+        if (d.planes) { d.planes = nullptr; d.leaf_state = s->leaf_state.as<uint8_t>(); }
+    }
     for (int i = 0; i < iters; i++) {
         if (i == 0 || d_active) {
             if (list) launch_select_list(st, d, list, count);
             else launch_select(st, d, d_active);
         }
         if (e->cfg.evaluator == TG_EVAL_RESNET) {
+            if (symm) { if (int rc = symm_search_leaves(e, d, leaves); rc) return rc; }
             float* pol = d.logits ? nullptr : d.policy;  // logits mode: the backup takes softmax / tanh itself
             int rc = d.planes ? net_forward_dev(e, leaves, d.planes, pol, d.eval) : net_forward_states_dev(e, leaves, d.leaf_state, pol, d.eval);
             if (rc) return rc;

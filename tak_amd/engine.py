@@ -138,6 +138,7 @@ ABI_SYMBOLS = [
     "tg_state_bytes", "tg_engine_create", "tg_engine_destroy", "tg_last_error", "tg_sync", "tg_stream", "tg_device_info", "tg_debug_switches",
     "tg_input_channels", "tg_policy_size", "tg_movegen", "tg_play", "tg_result", "tg_encode", "tg_move_index",
     "tg_perft", "tg_net_set_tensor", "tg_net_init_random", "tg_net_get_tensor", "tg_net_finalize", "tg_net_set_precision", "tg_policy_eval", "tg_forward_mcts", "tg_policy_eval_dev",
+    "tg_policy_eval_symm", "tg_policy_eval_symm_dev", "tg_symm_perm_read", "tg_search_set_symmetry", "tg_search_get_symmetry",
     "tg_search_create", "tg_search_reset", "tg_search_run", "tg_search_apply_dirichlet", "tg_search_apply_noise",
     "tg_search_root", "tg_search_play", "tg_search_states", "tg_search_dump", "tg_search_debug", "tg_search_counters", "tg_search_pool",
     "tg_selfplay_create", "tg_selfplay_step", "tg_selfplay_stats", "tg_selfplay_drain",
@@ -150,6 +151,17 @@ ABI_SYMBOLS = [
     "tg_train_grad_buffer", "tg_train_comm_stats", "tg_train_comm_info", "tg_train_comm_preflight", "tg_train_order", "tg_pit",
     "tg_format_move", "tg_parse_move", "tg_format_tps", "tg_parse_tps", "tg_format_example", "tg_parse_example",
 ]
+
+
+SYMM_OFF, SYMM_HASHED = 0, 1  # TgSearchSymmetry
+
+
+def _symmetry_mode(mode):
+    if isinstance(mode, str):
+        if mode not in ("off", "hashed"):
+            raise ValueError(f"symmetry must be 'off' or 'hashed', not {mode!r}")
+        return SYMM_HASHED if mode == "hashed" else SYMM_OFF
+    return int(mode)
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -318,10 +330,15 @@ def train_order(seed, n):
     return order
 
 
-def pit(new, old, pairs=128, rollouts=50, batch=16, idle_rollouts=1, random_plies=2, komi=2, max_plies=0, arena_nodes=0, seed=0):
+def pit(new, old, pairs=128, rollouts=50, batch=16, idle_rollouts=1, random_plies=2, komi=2, max_plies=0, arena_nodes=0, seed=0,
+        symmetry=None):
     """`pit(new, old)` of train/src/pit.rs on two engines (one per weight set) → dict(wins, losses, draws, win_rate, …; the
     ref_* entries are the counts with the reference's early exit, pit.rs:20-23, applied);
-    `rollouts` iterations of `batch` virtual rollouts per move (ROLLOUTS × BATCH_SIZE); 2·pairs·batch ≤ max_batch"""
+    `rollouts` iterations of `batch` virtual rollouts per move (ROLLOUTS × BATCH_SIZE); 2·pairs·batch ≤ max_batch
+    symmetry: SYMM_OFF / SYMM_HASHED (or "off" / "hashed") for both engines' searches of this match; None = each engine's own"""
+    if symmetry is not None:
+        new.search_set_symmetry(symmetry)
+        old.search_set_symmetry(symmetry)
     cfg = TgPitConfig(pairs, rollouts, idle_rollouts, random_plies, komi, max_plies, arena_nodes, batch, seed)
     res = TgPitResult()
     rc = load_library().tg_pit(new.h, old.h, C.byref(cfg), C.byref(res))
@@ -629,13 +646,38 @@ class Engine:
             self.set_tensor(k, np.asarray(v, np.float32))
         self._check(self.lib.tg_net_finalize(self.h))
 
-    def policy_eval(self, states):
-        """Network::policy_eval: states → (policy [k, P] softmax, eval [k] tanh)."""
+    def policy_eval(self, states, symmetries=None):
+        """Network::policy_eval: states → (policy [k, P] softmax, eval [k] tanh).
+        symmetries: a mask of dihedral images (bit s = image s of tg_augment_examples' order, 0xFF = all eight) → the mean of
+        the network's output over them, mapped back to each state's own orientation (tg_policy_eval_symm); None = the plain call"""
         states, k = self._states(states)
         policy = np.zeros((k, self.psize), np.float32)
         ev = np.zeros(k, np.float32)
-        self._check(self.lib.tg_policy_eval(self.h, k, _p(states), _p(policy), _p(ev)))
+        if symmetries is None:
+            self._check(self.lib.tg_policy_eval(self.h, k, _p(states), _p(policy), _p(ev)))
+        else:
+            self._check(self.lib.tg_policy_eval_symm(self.h, k, _p(states), C.c_uint32(int(symmetries)), _p(policy), _p(ev)))
         return policy, ev
+
+    def policy_eval_symm_dev(self, n, d_states, mask, d_policy, d_eval):
+        self._check(self.lib.tg_policy_eval_symm_dev(self.h, n, C.c_void_p(d_states), C.c_uint32(int(mask)), C.c_void_p(d_policy),
+                                                     C.c_void_p(d_eval)))
+
+    def symm_perm(self):
+        """the device's policy permutation tables [8, P] (tg_symm_perm_read): perm[s, j] = slot of the image under s of slot j's move"""
+        perm = np.zeros((8, self.psize), np.int32)
+        self._check(self.lib.tg_symm_perm_read(self.h, _p(perm)))
+        return perm
+
+    def search_set_symmetry(self, mode):
+        """tg_search_set_symmetry: SYMM_OFF / SYMM_HASHED (or "off" / "hashed") for the current search or self-play object"""
+        self._check(self.lib.tg_search_set_symmetry(self.h, _symmetry_mode(mode)))
+
+    def search_get_symmetry(self):
+        """(mode, leaves sent to the network under a non-identity image since the engine was created); synchronises"""
+        mode, count = C.c_int(0), C.c_uint64(0)
+        self._check(self.lib.tg_search_get_symmetry(self.h, C.byref(mode), C.byref(count)))
+        return mode.value, count.value
 
     def forward_mcts(self, planes):
         planes = np.ascontiguousarray(planes, np.float32).reshape(-1, self.cin, self.n, self.n)
@@ -649,11 +691,14 @@ class Engine:
         self._check(self.lib.tg_policy_eval_dev(self.h, n, C.c_void_p(d_states), C.c_void_p(d_policy), C.c_void_p(d_eval)))
 
     # ---- Node / search ----------------------------------------------------------------------------
-    def search_create(self, games, arena_nodes=1 << 16, base=500.0, init=4.0, seed=0, slot_base=0, batch=1, visit_limit=0):
-        """batch: virtual rollouts per tree and iteration (Player's batching); games * batch <= max_batch"""
+    def search_create(self, games, arena_nodes=1 << 16, base=500.0, init=4.0, seed=0, slot_base=0, batch=1, visit_limit=0, symmetry=None):
+        """batch: virtual rollouts per tree and iteration (Player's batching); games * batch <= max_batch
+        symmetry: SYMM_HASHED / "hashed" = one hashed dihedral image per evaluated leaf (search_set_symmetry); None = off"""
         cfg = TgSearchConfig(games, arena_nodes, base, init, seed, slot_base, batch, visit_limit, 0)
         self._check(self.lib.tg_search_create(self.h, C.byref(cfg)))
         self.games = games
+        if symmetry is not None and _symmetry_mode(symmetry) != SYMM_OFF:
+            self.search_set_symmetry(symmetry)
 
     def search_reset(self, states):
         states, k = self._states(states)
@@ -750,7 +795,7 @@ class Engine:
     # ---- self_play_parallel ------------------------------------------------------------------------
     def selfplay_create(self, games, arena_nodes=0, base=500.0, init=4.0, seed=0, rollouts=400, noise_plies=80,
                         exploit_plies=40, noise_alpha=0.2, noise_ratio=0.3, komi=2, total_games=0, max_examples=1 << 16,
-                        slot_base=0, max_game_plies=0, visit_limit=0, batch=1, boost_plies=0, boost_factor=1):
+                        slot_base=0, max_game_plies=0, visit_limit=0, batch=1, boost_plies=0, boost_factor=1, symmetry=None):
         """batch: virtual rollouts per game and iteration (Player's batching; the reference's self_play uses 32): `rollouts`
         iterations of `batch` rollouts per move, games * batch leaves per network call, games * batch <= max_batch
         boost_plies, boost_factor: the rollout schedule (QUAD_ROLLOUT_PLIES; the reference's self_play uses 10 and 4): a move
@@ -762,6 +807,8 @@ class Engine:
         self.games = games
         if boost_plies != 0 and boost_factor != 1:
             self.selfplay_set_schedule(boost_plies, boost_factor)
+        if symmetry is not None and _symmetry_mode(symmetry) != SYMM_OFF:  # (None / off: the setter is not called)
+            self.search_set_symmetry(symmetry)
 
     def selfplay_set_schedule(self, boost_plies, boost_factor, reserved=(0, 0)):
         """tg_selfplay_set_schedule as it is: after selfplay_create, before the first selfplay_step"""

@@ -8,13 +8,14 @@ updates as Player::rollout (player.rs:77-110, 125-128), without the thread.  The
 Players can share one engine only one at a time (the engine holds one search state)."""
 import numpy as np
 
-from .analysis import MAX_BRANCH_LENGTH, Analysis, NodeDebugInfo
+from .analysis import MAX_BRANCH_LENGTH, Analysis, NodeDebugInfo, root_eval
 from .engine import TG_MAX_MOVES
 
 
 class Player:
-    def __init__(self, engine, batch, save_examples, game, arena_nodes=1 << 16, seed=0, create_analysis=False):
-        """Player::new(network, batch, save_examples, create_analysis, &game); `game` is a packed state."""
+    def __init__(self, engine, batch, save_examples, game, arena_nodes=1 << 16, seed=0, create_analysis=False, symmetry=None):
+        """Player::new(network, batch, save_examples, create_analysis, &game); `game` is a packed state.
+        symmetry: "hashed" / SYMM_HASHED = every evaluated leaf goes to the network as a hashed dihedral image (Engine.search_set_symmetry)"""
         self.e = engine
         self.batch = int(batch)
         self.save_examples = bool(save_examples)
@@ -25,7 +26,7 @@ class Player:
         hdr = game[engine.sb - 16:]
         self.analysis = Analysis(engine.n, int(hdr[8:9].view(np.int8)[0]), int(hdr[2:4].view("<u2")[0]))
         self.rng = np.random.default_rng(seed)
-        engine.search_create(1, arena_nodes=arena_nodes, seed=seed, batch=self.batch)
+        engine.search_create(1, arena_nodes=arena_nodes, seed=seed, batch=self.batch, symmetry=symmetry)
         engine.search_reset(np.ascontiguousarray(game, np.uint8).reshape(1, -1))
         self.rollout()  # the reference requests the first batch in the constructor (player.rs:65-66)
 
@@ -62,6 +63,11 @@ class Player:
         """Node::debug(depth) of the root (player.rs:113-115): one tg_search_debug call, every child's continuation"""
         r = self.e.search_debug(depth, TG_MAX_MOVES)
         return NodeDebugInfo.from_search_debug(self.e.n, r, 0)
+
+    def root_eval(self, ensemble=True):
+        """(policy [P], eval) of the network on the current root; ensemble: the mean over all 8 dihedral images (analysis.root_eval)"""
+        p, v = root_eval(self.e, self.state(), ensemble=ensemble)
+        return p[0], float(v[0])
 
     def play_move(self, move, game=None, with_info=True):
         """Advance the tree (tree reuse) and the game; record an IncompleteExample and update the analysis (player.rs:136-166)."""
