@@ -423,6 +423,61 @@ TG_API int tg_search_counters(TgEngine* e, uint64_t* expansions, uint64_t* evals
 TG_API int tg_search_pool(TgEngine* e, uint64_t* nodes_total, uint64_t* nodes_in_use, uint64_t* nodes_peak);
 
 /* ---------------------------------------------------------------------------------------
+ * Forced wins: an exact depth-limited AND/OR search over Game::possible_moves / play / result
+ * (solve_kernels.hip).  A capability beside the MCTS, not a part of it: no network, no tree.
+ *
+ * For an ongoing position s with mover m, s_a is the position after legal move a:
+ *   W(s, L) "the mover wins within L plies": false for L <= 0, else some a has result(s_a) = a win of m (road or flats) or
+ *           has s_a ongoing and X(s_a, L-1).
+ *   X(s, L) "the mover loses within L plies": false for L <= 0, else EVERY a has result(s_a) = a win of the opponent (a move
+ *           that completes only the opponent's road) or has s_a ongoing and W(s_a, L-1).
+ *   A draw (either kind, the reversible-plies rule included) proves nothing for either side.
+ * move_values[a]: +1 wins at once, -1 loses at once, +(1+k) for the least k with X(s_a, k), -(1+k) for the least k with
+ *   W(s_a, k), 0 if none of these holds with 1+k <= depth.
+ * value: +d with d the smallest positive move value; -d with d the largest |move value| if ALL moves are negative; else 0.
+ * best: the first move (possible_moves order) with the smallest positive value; in a lost position the first move with the
+ *   largest |value| (the longest defence); 0 when value is 0.
+ * The levels L = 1, 2, ... are deepened in turn, one launch each.  Without TG_SOLVE_ALL_MOVES a position stops at the first
+ * level that decides it (some move wins, or all moves lose): move values that need more plies stay 0.  With it every level
+ * up to `depth` runs and the move table is complete.  "Forced win" means by road OR by flats, not a road-only tinue.
+ * A finished position, an inactive or a dead game gives counts 0, value 0, best 0.
+ *
+ * node_budget: positions one work item = (position, root move, level) may create before it gives up that level; the move
+ *   stays unproven at that level and may be proven at a later one.  budget_hit[i] = 1 if any item of position i gave up.
+ *   With budget_hit 0 the outputs are exactly the definitions above.  With budget_hit 1 every non-zero entry is still a
+ *   sound proof: the sign of the exact answer at the same depth, |d| >= the exact |d|; nothing else is promised.
+ *   nodes[i] (positions created by play for position i) <= counts[i] * depth * (node_budget + TG_MAX_MOVES).
+ *   0 = TG_SOLVE_DEFAULT_BUDGET, which exists so that no launch on a shared card can run away; values above 2^31 - 1
+ *   count as 2^31 - 1.  The default is 2^10, fixed by scripts/bench_solve.py on an MI355X (profiles/r18_b_solve.json): the
+ *   largest power of two that keeps the longest level launch at depth 5 on its two inputs of 4096 positions under
+ *   100 ms — 69 ms (mid-game) and 45 ms (near the end) at 2^10, 156 ms and 86 ms at 2^11.  At the default most unproven
+ *   depth-5 positions report budget_hit; a caller who can wait passes a larger budget (2^22 gave up nowhere on those
+ *   inputs: 3.3 to 4.1 s per 4096 positions).
+ *
+ * moves / move_values: n x TG_MAX_MOVES, zero past counts[i]; every other output: n.  Any output pointer may be NULL.
+ * tg_solve validates the states on the host as tg_search_reset does; it needs no network and no search object.
+ * tg_search_solve solves the current roots of the live search / self-play object in place (no host copy of the states,
+ * the trees are not touched); without such an object TG_ERR_STATE.  active: games mask or NULL = all.
+ * Both synchronise before they return.  TG_ERR_INVALID_ARG names the field: depth outside 1 .. TG_SOLVE_MAX_DEPTH, unknown
+ * flags, non-zero reserved, NULL states with n > 0.
+ * ------------------------------------------------------------------------------------- */
+#define TG_SOLVE_MAX_DEPTH 6
+#define TG_SOLVE_ALL_MOVES 1u
+#define TG_SOLVE_DEFAULT_BUDGET (1 << 10)
+typedef struct TgSolveConfig {
+    int32_t depth;         /* 1 .. TG_SOLVE_MAX_DEPTH */
+    uint32_t flags;        /* TG_SOLVE_ALL_MOVES */
+    uint64_t node_budget;  /* positions a single (position, root move, level) work item may create before it gives up; 0 = default */
+    int32_t reserved[4];   /* must be 0 */
+} TgSolveConfig;
+TG_API int tg_solve(TgEngine* e, int n, const void* states, const TgSolveConfig* cfg,
+                    int8_t* value, TgMove* best, int32_t* counts, TgMove* moves, int8_t* move_values,
+                    uint8_t* budget_hit, uint64_t* nodes);
+TG_API int tg_search_solve(TgEngine* e, const TgSolveConfig* cfg, const uint8_t* active,
+                           int8_t* value, TgMove* best, int32_t* counts, TgMove* moves, int8_t* move_values,
+                           uint8_t* budget_hit, uint64_t* nodes);
+
+/* ---------------------------------------------------------------------------------------
  * Self-play driver (replaces self_play_parallel, train/src/self_play.rs:96-262).
  * All compile-time constants of the reference (self_play.rs:10-19,94) are runtime here.
  * ------------------------------------------------------------------------------------- */

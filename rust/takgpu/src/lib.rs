@@ -10,6 +10,7 @@
 //! | `self_play_parallel` — train/src/self_play.rs:96-262         | [`selfplay::self_play_parallel_gpu`]   |
 //! | `examples` of `training_loop` — train/src/main.rs:26,56-123 | [`window`]: `GpuNet::window_*`         |
 //! | `pit` — train/src/pit.rs:15-96                               | [`pit::pit_gpu`]                       |
+//! | the instant-win scan — train/src/self_play.rs:118-171, deepened to forced wins | [`solve`]: `GpuNet::solve`  |
 //! | `Game<N>` / `Move` / `Example<N>` — tak/src/game.rs:24-35, takparse, alpha-tak/src/example.rs:29-33 | [`pack`] |
 //!
 //! `train/src/main.rs` then reads `train::<5, GpuNet<5>>(args)` and calls `self_play_parallel_gpu(&network)` at :120 and
@@ -19,6 +20,7 @@ pub mod net;
 pub mod pack;
 pub mod pit;
 pub mod selfplay;
+pub mod solve;
 pub mod window;
 
 use std::ffi::CStr;
@@ -26,6 +28,7 @@ use std::ffi::CStr;
 pub use net::GpuNet;
 pub use pit::pit_gpu;
 pub use selfplay::{self_play_parallel_gpu, SelfPlaySettings};
+pub use solve::Solved;
 pub use takgpu_sys as sys;
 
 /// A failed C-ABI call: the negative `TgStatus` and the library's thread-local message.

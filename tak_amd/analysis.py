@@ -142,6 +142,7 @@ class Analysis:
         self.branches = []   # (ply, MoveInfo)
         self.evals = []      # np.float32
         self.marks = []      # (ply, kind)
+        self.tactics = {}    # index into played_moves → (suffix after the move, comment): annotate_tactics, opt-in
 
     @classmethod
     def default(cls, board_size):
@@ -178,6 +179,31 @@ class Analysis:
             elif np.float32(info.visits) > np.float32(np.float32(top) * CANDIDATE_MOVE_RATIO):
                 self.branches.append((ply, info))
 
+    def annotate_tactics(self, solver, state, played_move, depth, node_budget=1 << 16):
+        """Opt-in tactical annotation of the move just recorded (call after update / add_move): `solver` (an Engine) solves
+        the position after `played_move` from `state` at `depth` plies (Engine.solve).
+          the opponent is proven lost      → `"` after the move, before any ?/! mark, and the comment {forced win in k}
+          the move itself is proven losing → the comment {loses in k}
+          otherwise, from ply 2 on (the first two plies place the opponent's stone), `'` (Tak) when the mover would win at
+          once if it were their turn again: a depth-1 solve of the same position with the header's to_move byte flipped.
+        k counts the plies after the move.  `"` here means a forced win by road OR by flats within `depth` plies — not a
+        road-only tinuë, which PTN's mark strictly stands for.  node_budget: Engine.solve's (one position: see player.TACTICS_BUDGET);
+        a proof the budget cuts off is a missing mark, never a wrong one."""
+        k = len(self.played_moves) - 1
+        if k < 0 or self.played_moves[k] != int(played_move) or self.move_info[k] is None:
+            return
+        after, _ = solver.play(np.ascontiguousarray(state, np.uint8).reshape(1, -1), np.array([played_move], np.uint16))
+        value = int(solver.solve(after, int(depth), node_budget=int(node_budget))["value"][0])
+        if value < 0:
+            self.tactics[k] = ('"', f" {{forced win in {-value}}}")
+        elif value > 0:
+            self.tactics[k] = ("", f" {{loses in {value}}}")
+        elif self.start_ply + k >= 2:
+            again = np.array(after, np.uint8, copy=True)
+            again[0, again.shape[1] - 16 + 1] ^= 1  # TgHeader.to_move
+            if int(solver.solve(again, 1, node_budget=int(node_budget))["value"][0]) > 0:
+                self.tactics[k] = ("'", "")
+
     def without_branches(self):
         a = Analysis.default(self.n)
         a.__dict__.update({k: list(v) if isinstance(v, list) else v for k, v in self.__dict__.items()})
@@ -197,6 +223,9 @@ class Analysis:
             nonlocal mi
             info = self.move_info[k]
             s = format_move(self.n, self.played_moves[k])
+            tac = self.tactics.get(k)
+            if tac:
+                s += tac[0]
             if mi < len(marks) and marks[mi][0] == ply:
                 s += _MARKS[marks[mi][1]]
                 mi += 1
@@ -206,6 +235,8 @@ class Analysis:
                     ev = np.float32(ev * np.float32(-1.0)) if flip_eval else ev
                     s += f"{{evaluation: {fmt_f32(ev, 3, True)}}}"
                 s += info.ptn_comment(not flip_eval)
+            if tac:
+                s += tac[1]
             return s
 
         k = 0

@@ -62,6 +62,7 @@ struct Net;     // net.hip
 struct Search;  // search_host.h
 struct Trainer; // train.hip
 struct Window;  // window.hip
+struct Solver;  // solve.hip
 struct WindowDev;  // kernels.h
 struct SearchDev;  // search.cuh
 
@@ -86,6 +87,7 @@ struct TgEngine {
     // staging (the caller's states; the folded outputs), the search's mode (TgSearchSymmetry) and its count of transformed leaves
     tg::DevBuf symm_perm, symm_src, symm_policy, symm_eval, symm_count;
     int symm_mode = 0;
+    tg::Solver* solver = nullptr;  // forced-win solver scratch (tg_solve / tg_search_solve): created at the first call, dies with the engine
     ~TgEngine();
 };
 
@@ -122,6 +124,8 @@ int train_window(TgEngine* e, const WindowDev& W, uint32_t row0, int count, uint
                  int32_t* steps);
 // window.hip
 void window_destroy(Window* w);
+// solve.hip
+void solver_destroy(Solver* s);
 // symm.hip
 int symm_tables_build(TgEngine* e);  // (tg_net_finalize) the device tables behind tg_policy_eval_symm and TG_SYMM_HASHED, built once
 // (search_iterate) the hashed image of the iteration's leaves, between the tree kernel and the forward; TG_SYMM_OFF: nothing

@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get("TAKGPU_LIB") or os.path.join(_HERE, "libtakgpu.so")  
 TG_ABI_VERSION = 5
 TG_MAX_MOVES = 512
 TG_DEBUG_MAX_DEPTH = 64
+TG_SOLVE_MAX_DEPTH = 6
+TG_SOLVE_ALL_MOVES = 1
 HEAD_FC5, HEAD_CONV = 0, 1
 EVAL_RESNET, EVAL_DUMMY, EVAL_HASH = 0, 1, 2
 
@@ -36,6 +38,10 @@ class TgSearchConfig(C.Structure):
     _fields_ = [("games", C.c_int32), ("arena_nodes", C.c_int32), ("exploration_base", C.c_float),
                 ("exploration_init", C.c_float), ("seed", C.c_uint64), ("slot_base", C.c_uint32), ("batch", C.c_uint32),
                 ("visit_limit", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TgSolveConfig(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("flags", C.c_uint32), ("node_budget", C.c_uint64), ("reserved", C.c_int32 * 4)]
 
 
 class TgProfile(C.Structure):
@@ -141,6 +147,7 @@ ABI_SYMBOLS = [
     "tg_policy_eval_symm", "tg_policy_eval_symm_dev", "tg_symm_perm_read", "tg_search_set_symmetry", "tg_search_get_symmetry",
     "tg_search_create", "tg_search_reset", "tg_search_run", "tg_search_apply_dirichlet", "tg_search_apply_noise",
     "tg_search_root", "tg_search_play", "tg_search_states", "tg_search_dump", "tg_search_debug", "tg_search_counters", "tg_search_pool",
+    "tg_solve", "tg_search_solve",
     "tg_selfplay_create", "tg_selfplay_step", "tg_selfplay_stats", "tg_selfplay_drain",
     "tg_selfplay_set_schedule", "tg_selfplay_schedule_stats",
     "tg_window_create", "tg_window_info", "tg_window_clear", "tg_window_absorb", "tg_window_push", "tg_window_read", "tg_window_train",
@@ -760,6 +767,33 @@ class Engine:
                                              _p(ev), _p(cont_moves), _p(cont_visits), _p(cont_len)))
         return dict(moves=moves, visits=visits, reward=reward, policy=policy, counts=counts, eval=ev, cont_moves=cont_moves,
                     cont_visits=cont_visits, cont_len=cont_len)
+
+    # ---- forced wins (tg_solve / tg_search_solve) ----------------------------------------------------
+    def _solve_out(self, k):
+        return dict(value=np.zeros(k, np.int8), best=np.zeros(k, np.uint16), counts=np.zeros(k, np.int32),
+                    moves=np.zeros((k, TG_MAX_MOVES), np.uint16), move_values=np.zeros((k, TG_MAX_MOVES), np.int8),
+                    budget_hit=np.zeros(k, np.uint8), nodes=np.zeros(k, np.uint64))
+
+    def solve(self, states, depth, all_moves=False, node_budget=0, flags=None):
+        """Exact forced wins within `depth` plies of every position (definitions: include/takgpu.h).  Returns a dict of arrays:
+        value / best / counts / budget_hit / nodes [k], moves / move_values [k, TG_MAX_MOVES] (zero past counts).
+        all_moves: deepen every position to `depth` and complete the move table instead of stopping at the deciding level;
+        node_budget: positions one (position, root move, level) may create, 0 = the library's default; flags overrides all_moves."""
+        states, k = self._states(states)
+        cfg = TgSolveConfig(int(depth), (TG_SOLVE_ALL_MOVES if all_moves else 0) if flags is None else int(flags), int(node_budget))
+        o = self._solve_out(k)
+        self._check(self.lib.tg_solve(self.h, k, _p(states), C.byref(cfg), _p(o["value"]), _p(o["best"]), _p(o["counts"]), _p(o["moves"]),
+                                      _p(o["move_values"]), _p(o["budget_hit"]), _p(o["nodes"])))
+        return o
+
+    def search_solve(self, depth, active=None, all_moves=False, node_budget=0):
+        """Engine.solve on the current roots of the live search / self-play object, in place on the device; games outside
+        `active` and dead games give zero rows.  The trees are not touched."""
+        cfg = TgSolveConfig(int(depth), TG_SOLVE_ALL_MOVES if all_moves else 0, int(node_budget))
+        o = self._solve_out(self.games)
+        self._check(self.lib.tg_search_solve(self.h, C.byref(cfg), _p(_mask(active)), _p(o["value"]), _p(o["best"]), _p(o["counts"]),
+                                             _p(o["moves"]), _p(o["move_values"]), _p(o["budget_hit"]), _p(o["nodes"])))
+        return o
 
     def search_counters(self):
         a, b = C.c_uint64(0), C.c_uint64(0)

@@ -11,12 +11,25 @@ import numpy as np
 from .analysis import MAX_BRANCH_LENGTH, Analysis, NodeDebugInfo, root_eval
 from .engine import TG_MAX_MOVES
 
+# node_budget of a Player's solver calls.  The library's default (2^10) is sized so that a launch over thousands of positions stays
+# short on a shared card; it cannot finish the proof of a loss two plies deep (every reply × every answer: ≈ 60² positions).  A
+# player solves ONE root, about a hundred work items: 2^16 positions each finish any depth-3 proof and bound a level at a fraction
+# of a second.
+TACTICS_BUDGET = 1 << 16
+
 
 class Player:
-    def __init__(self, engine, batch, save_examples, game, arena_nodes=1 << 16, seed=0, create_analysis=False, symmetry=None):
+    def __init__(self, engine, batch, save_examples, game, arena_nodes=1 << 16, seed=0, create_analysis=False, symmetry=None, tactics=0,
+                 tactics_budget=TACTICS_BUDGET):
         """Player::new(network, batch, save_examples, create_analysis, &game); `game` is a packed state.
-        symmetry: "hashed" / SYMM_HASHED = every evaluated leaf goes to the network as a hashed dihedral image (Engine.search_set_symmetry)"""
+        symmetry: "hashed" / SYMM_HASHED = every evaluated leaf goes to the network as a hashed dihedral image (Engine.search_set_symmetry)
+        tactics: D > 0 = the analysis annotates every played move that has info with the forced-win solver at depth D (Analysis.annotate_tactics);
+        0 (default) = no solver call anywhere
+        tactics_budget: node_budget of this player's solver calls (pick_move's and the annotation's)"""
         self.e = engine
+        self.tactics = int(tactics)
+        self.tactics_budget = int(tactics_budget)
+        self.last_tactics = None  # the Engine.search_solve result of the last pick_move(…, tactics > 0)
         self.batch = int(batch)
         self.save_examples = bool(save_examples)
         self.create_analysis = bool(create_analysis)
@@ -47,11 +60,23 @@ class Player:
         c = int(r["counts"][0])
         return r["moves"][0, :c].copy(), r["visits"][0, :c].copy()
 
-    def pick_move(self, exploitation):
-        """Node::pick_move (play.rs:49-67): most visited (last on ties) or sampled ∝ visits."""
+    def pick_move(self, exploitation, tactics=0):
+        """Node::pick_move (play.rs:49-67): most visited (last on ties) or sampled ∝ visits.
+        tactics = D > 0: first solve the root at depth D (Engine.search_solve).  A proven win returns its `best` move; otherwise
+        the moves with a proven loss leave the candidates (unless every move is one).  0: no solver call, the reference's pick."""
         moves, visits = self.improved_policy()
         if len(moves) == 0:
             raise RuntimeError("pick_move on a root without children")
+        if tactics > 0:
+            r = self.last_tactics = self.e.search_solve(int(tactics), node_budget=self.tactics_budget)
+            if int(r["value"][0]) > 0:
+                return int(r["best"][0])
+            c = int(r["counts"][0])
+            if c != len(moves) or not np.array_equal(r["moves"][0, :c], moves):
+                raise RuntimeError("pick_move: the root's children are not the solver's move list")
+            keep = r["move_values"][0, :c] >= 0
+            if keep.any():
+                moves, visits = moves[keep], visits[keep]
         if exploitation:
             return int(moves[len(visits) - 1 - int(np.argmax(visits[::-1]))])
         total = int(visits.sum())
@@ -77,6 +102,8 @@ class Player:
         if self.create_analysis:
             if with_info:
                 self.analysis.update(self.debug(MAX_BRANCH_LENGTH), move)
+                if self.tactics > 0:
+                    self.analysis.annotate_tactics(self.e, self.state(), move, self.tactics, node_budget=self.tactics_budget)
             else:
                 self.analysis.add_move_without_info(move)
         self.e.search_play(np.array([move], np.uint16))

@@ -1,0 +1,215 @@
+"""Reference for the forced-win solver (tg_solve): the definitions of include/takgpu.h stated in plain Python on the CPU
+rules (oracle.movegen / play / result).  Nothing here follows the kernels' structure: W and X are the two recursive
+predicates, a move's value is the least level at which one of them holds, and the early stop is a clip of those values.
+
+    W(s, L)  the mover wins within L plies      X(s, L)  the mover loses within L plies
+
+`Ref(n, variant=...)` plants one deliberate mistake (VARIANTS) — the teeth tests check that `compare`, the comparison the
+GPU tests use, rejects each of them."""
+import functools
+
+import numpy as np
+
+from oracle import oracle
+
+TG_MAX_MOVES = 512
+VARIANTS = ("no_suicide", "draw_is_loss", "min_at_lost", "last_best", "no_early_stop")
+FIELDS = ("value", "best", "counts", "moves", "move_values")
+
+
+class Ref:
+    """W, X and the move values on arrays of positions: W(S, L)[i] / X(S, L)[i] is the predicate on the ongoing position S[i]."""
+    CHUNK = 2048  # positions expanded at once (bounds the memory of one batch of children)
+
+    def __init__(self, n, variant=None):
+        assert variant is None or variant in VARIANTS
+        self.n = n
+        self.sb = oracle.state_bytes(n)
+        self.variant = variant
+        self.nodes = 0  # children generated
+
+    def mover(self, S):
+        return S[:, self.sb - 16 + 1].astype(np.int64)
+
+    @staticmethod
+    def won(res, color):
+        return np.where(color == 0, (res == 1) | (res == 2), (res == 3) | (res == 4))
+
+    def lost_at_once(self, res, m):
+        """the move just played by m ends the game against m"""
+        lost = self.won(res, m ^ 1)
+        if self.variant == "no_suicide":
+            lost = np.zeros_like(lost)
+        if self.variant == "draw_is_loss":
+            lost = lost | (res >= 5)
+        return lost
+
+    def play(self, S, moves):
+        ch, status = oracle.play(self.n, S, moves)
+        assert not status.any()
+        self.nodes += len(ch)
+        return ch, oracle.result(self.n, ch)
+
+    def W(self, S, L):
+        """some move wins at once, or leads to an ongoing position that is X within L - 1"""
+        k = len(S)
+        if L <= 0 or k == 0:
+            return np.zeros(k, bool)
+        if k > self.CHUNK:
+            return np.concatenate([self.W(S[i:i + self.CHUNK], L) for i in range(0, k, self.CHUNK)])
+        moves, counts = oracle.movegen(self.n, S)
+        assert counts.max() <= TG_MAX_MOVES
+        idx = np.repeat(np.arange(k), counts)
+        col = np.arange(len(idx)) - np.repeat(np.cumsum(counts) - counts, counts)
+        ch, res = self.play(S[idx], moves[idx, col])
+        out = np.zeros(k, bool)
+        out[idx[self.won(res, self.mover(S)[idx])]] = True
+        if L > 1:
+            cand = np.nonzero((res == 0) & ~out[idx])[0]
+            out[idx[cand[self.X(ch[cand], L - 1)]]] = True
+        return out
+
+    def X(self, S, L):
+        """every move loses at once, or leads to an ongoing position that is W within L - 1 (move by move: a position leaves
+        the test at its first move that does neither)"""
+        k = len(S)
+        if L <= 0 or k == 0:
+            return np.zeros(k, bool)
+        moves, counts = oracle.movegen(self.n, S)
+        out = np.ones(k, bool)
+        m = self.mover(S)
+        alive, j = np.arange(k), 0
+        while True:
+            alive = alive[counts[alive] > j]
+            if not len(alive):
+                return out
+            ch, res = self.play(S[alive], moves[alive, j])
+            ok = self.lost_at_once(res, m[alive])
+            if L > 1:
+                cand = np.nonzero((res == 0) & ~ok)[0]
+                ok[cand[self.W(ch[cand], L - 1)]] = True
+            out[alive[~ok]] = False
+            alive, j = alive[ok], j + 1
+
+    def fold(self, moves, vals):
+        """(value, best) of a position from its move values"""
+        pos = [v for v in vals if v > 0]
+        if pos:
+            value = min(pos)
+        elif len(vals) and all(v < 0 for v in vals):
+            value = -(min if self.variant == "min_at_lost" else max)(-v for v in vals)
+        else:
+            return 0, 0
+        hits = [a for a, v in enumerate(vals) if v == value]
+        return value, int(moves[hits[-1] if self.variant == "last_best" else hits[0]])
+
+    def solve_one(self, s, depth, all_moves):
+        """→ (value, best, moves, move_values).  Level L gives a still unvalued move a the value +L if X(s_a, L - 1), else
+        -L if W(s_a, L - 1): the least k of the definition, found by trying k = 0, 1, … in turn."""
+        s = np.ascontiguousarray(s, np.uint8).reshape(1, -1)
+        if int(oracle.result(self.n, s)[0]) != 0:
+            return 0, 0, np.zeros(0, np.uint16), []
+        moves, counts = oracle.movegen(self.n, s)
+        c = int(counts[0])
+        assert c <= TG_MAX_MOVES
+        moves = moves[0, :c]
+        ch, res = self.play(np.repeat(s, c, axis=0), moves)
+        m = self.mover(s).repeat(c)
+        vals = np.zeros(c, np.int64)
+        vals[self.lost_at_once(res, m)] = -1
+        vals[self.won(res, m)] = 1
+        stop_early = not (all_moves or self.variant == "no_early_stop")
+        for level in range(1, depth + 1):  # the levels run: L* is the first that decides the position, or depth
+            if level > 1:
+                pend = np.nonzero((res == 0) & (vals == 0))[0]
+                vals[pend[self.X(ch[pend], level - 1)]] = level
+                pend = pend[vals[pend] == 0]
+                vals[pend[self.W(ch[pend], level - 1)]] = -level
+            value, best = self.fold(moves, [int(v) for v in vals])
+            if stop_early and value != 0:
+                break
+        return value, best, moves, [int(v) for v in vals]
+
+    def solve(self, states, depth, all_moves=False):
+        states = np.ascontiguousarray(states, np.uint8).reshape(-1, self.sb)
+        k = len(states)
+        out = dict(value=np.zeros(k, np.int8), best=np.zeros(k, np.uint16), counts=np.zeros(k, np.int32),
+                   moves=np.zeros((k, TG_MAX_MOVES), np.uint16), move_values=np.zeros((k, TG_MAX_MOVES), np.int8),
+                   nodes=np.zeros(k, np.uint64))
+        for i in range(k):
+            before = self.nodes
+            value, best, moves, vals = self.solve_one(states[i], depth, all_moves)
+            c = len(moves)
+            out["value"][i], out["best"][i], out["counts"][i] = value, best, c
+            out["moves"][i, :c] = moves
+            out["move_values"][i, :c] = vals
+            out["nodes"][i] = self.nodes - before
+        return out
+
+
+def compare(ref, got, budget_free=True):
+    """the comparison of the GPU tests: every field of FIELDS equal, row for row; with budget_free also budget_hit == 0.
+    Returns the list of differences (empty = equal)."""
+    bad = []
+    for f in FIELDS:
+        a, b = np.asarray(ref[f]), np.asarray(got[f])
+        if a.shape != b.shape:
+            bad.append(f"{f}: shape {a.shape} != {b.shape}")
+            continue
+        rows = np.nonzero((a != b).reshape(len(a), -1).any(axis=1))[0]
+        if len(rows):
+            bad.append(f"{f}: {len(rows)} rows differ, first {int(rows[0])}: expected {a[rows[0]].ravel()[:12]} got {b[rows[0]].ravel()[:12]}")
+    if budget_free and "budget_hit" in got and np.asarray(got["budget_hit"]).any():
+        bad.append(f"budget_hit set for {int(np.count_nonzero(got['budget_hit']))} positions")
+    return bad
+
+
+def class_counts(values):
+    """{proven value: positions}"""
+    v, c = np.unique(np.asarray(values), return_counts=True)
+    return {int(a): int(b) for a, b in zip(v, c)}
+
+
+def require_classes(values, classes):
+    """the condition of a test's set: at least 2 positions of every class the test claims to cover"""
+    cc = class_counts(values)
+    missing = {c: cc.get(c, 0) for c in classes if cc.get(c, 0) < 2}
+    assert not missing, f"the set holds fewer than 2 positions of {missing}: {cc}"
+
+
+def clip(out, depth):
+    """an ALL_MOVES result at a larger depth cut down to `depth`: what ALL_MOVES at `depth` must give"""
+    mv = np.where(np.abs(out["move_values"]) <= depth, out["move_values"], 0).astype(np.int8)
+    r = Ref(5)  # (fold needs no board)
+    o = dict(out, move_values=mv, value=out["value"].copy(), best=out["best"].copy())
+    for i in range(len(mv)):
+        c = int(out["counts"][i])
+        o["value"][i], o["best"][i] = r.fold(out["moves"][i, :c], [int(x) for x in mv[i, :c]])
+    return o
+
+
+# ---- the position sets of the tests (each computed once per process) --------------------------------------------------
+SETS = {
+    "p5_400": lambda: oracle.playouts(5, 400, 7)["prev"],
+    "r5_400": lambda: oracle.random_positions(5, 400, 3, 40),
+    "p5_160": lambda: oracle.playouts(5, 160, 7)["prev"],
+    "p6_200": lambda: oracle.playouts(6, 200, 7)["prev"],
+    "p6_80": lambda: oracle.playouts(6, 80, 7)["prev"],
+    "s5_200": lambda: oracle.playouts(5, 200, 11, style=3)["prev"],
+}
+BOARD = {"p5_400": 5, "r5_400": 5, "p5_160": 5, "p6_200": 6, "p6_80": 6, "s5_200": 5}
+
+
+@functools.lru_cache(maxsize=None)
+def positions(name):
+    a = SETS[name]()
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, depth, all_moves, variant=None):
+    out = Ref(BOARD[name], variant).solve(positions(name), depth, all_moves)
+    for v in out.values():
+        v.setflags(write=False)
+    return out
