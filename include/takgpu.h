@@ -365,6 +365,48 @@ TG_API int tg_search_run(TgEngine* e, int iters, const uint8_t* active);
 typedef enum TgSearchSymmetry { TG_SYMM_OFF = 0, TG_SYMM_HASHED = 1 } TgSearchSymmetry;
 TG_API int tg_search_set_symmetry(TgEngine* e, int mode);
 TG_API int tg_search_get_symmetry(TgEngine* e, int* mode, uint64_t* leaves_transformed);
+/* Proven values inside the tree (the MCTS-solver backup of Winands et al.).  No counterpart in the reference, whose tree keeps
+ * the result of a finished position in its node (mcts.rs:35-38) and never draws the conclusion one level up.
+ *   Node status, from the result code of a node (TgNodeRecord.result): W for TG_WHITE_ROAD, TG_WHITE_FLAT, TG_PROVEN_WHITE; B
+ *     likewise for black; D for TG_DRAW, TG_DRAW_REVERSIBLE, TG_PROVEN_DRAW; unknown otherwise (an uninitialised child is
+ *     unknown).  The TG_PROVEN_* codes are node-record codes, never a game's result: tg_result, the examples and the self-play
+ *     statistics never carry them.  They name colours, not "win / loss".
+ *   The rule, for an initialised ongoing node X whose side to move has colour c: some child has status c → X becomes
+ *     TG_PROVEN_c; else, if no child is unknown, X becomes TG_PROVEN_DRAW if some child is D and TG_PROVEN_(opponent of c)
+ *     otherwise; else nothing.  A proven node keeps its child count and its children.
+ *   TG_PROOF_ON: a rollout that has just initialised a finished position applies the rule to the path upward from that
+ *     node's parent, stopping at the first node that stays unknown; the root may be proven.  Nothing else changes a status.
+ *     A rollout that reaches a proven node ends there and backs up ±1 / 0 by its colour, like a finished position's; the
+ *     node's q and visits are not rewritten when it is proven.  With batch > 1 the passes of an iteration run in order, and a
+ *     status written by one pass is seen by the next.  At every return of tg_search_run / tg_selfplay_step the tree of a game
+ *     searched under TG_PROOF_ON since its last reset is closed under the rule: every proven node satisfies it and no
+ *     unproven initialised node does.  tg_search_play carries the statuses with the subtree.
+ *   The mode may be set at any time; on a tree that already has visits the statuses appear only from the next rollout that
+ *     initialises a finished position on, so the closure holds only for trees searched under TG_PROOF_ON from their reset.
+ *     Back to TG_PROOF_OFF: the rollouts of the off mode know the TgResult codes alone and would back a proven node up as a
+ *     draw, so once an iteration has run under TG_PROOF_ON the mode is turned off only after a tg_search_reset (before the next
+ *     iteration) or by a new create; otherwise TG_ERR_STATE and the mode stays on.  A self-play object has no reset: create anew.
+ *     It is sticky for the search / self-play object — tg_search_run and tg_selfplay_step, any evaluator, any batch, dense and
+ *     compacted iterations — and the next tg_search_create / tg_selfplay_create resets it to TG_PROOF_OFF (the default: the
+ *     engine without any of this).  tg_pit creates its own searches and runs them with TG_PROOF_OFF.
+ *     Without a search object TG_ERR_STATE; an unknown mode → TG_ERR_INVALID_ARG.
+ *   Self-play under TG_PROOF_ON picks its move proof-aware.  With m the root's colour to move:
+ *     1. if some root child has status m, the move is, among those children, the most visited, the LAST on ties, whatever
+ *        the temperature;
+ *     2. otherwise the candidates are the children whose status is not the opponent's colour, all children if that leaves
+ *        none, and pick_move (play.rs:49-67) runs on the candidates: exploit → most visited, last on ties; explore → the
+ *        draw over the visits with the other children's visits taken as 0; candidates without any visit → exploit over them.
+ *     The example keeps the root's real visits.
+ *   tg_search_get_proof: the mode, the nodes proven and the rollouts that ended on a proven node since tg_search_create /
+ *     tg_selfplay_create (synchronises; any pointer may be NULL).
+ *   tg_search_proof: root_status: games bytes, the result code of every root; child_status: games × TG_MAX_MOVES bytes, the
+ *     code of every root child in possible_moves order (0, a TgResult or a TgProven), zero past counts[g]; counts: games.
+ *     Any pointer may be NULL.  Synchronises. */
+typedef enum TgProven { TG_PROVEN_WHITE = 8, TG_PROVEN_BLACK = 9, TG_PROVEN_DRAW = 10 } TgProven;
+typedef enum TgSearchProof { TG_PROOF_OFF = 0, TG_PROOF_ON = 1 } TgSearchProof;
+TG_API int tg_search_set_proof(TgEngine* e, int mode);
+TG_API int tg_search_get_proof(TgEngine* e, int* mode, uint64_t* nodes_proven, uint64_t* rollouts_ended_on_proven);
+TG_API int tg_search_proof(TgEngine* e, uint8_t* root_status, uint8_t* child_status, int32_t* counts);
 /* Node::apply_dirichlet (noise.rs:6-16) on every active root with engine RNG
  * (stream = (seed, game, ply)). */
 TG_API int tg_search_apply_dirichlet(TgEngine* e, float alpha, float ratio, const uint8_t* active);
@@ -385,7 +427,8 @@ TG_API int tg_search_play(TgEngine* e, const TgMove* moves, const uint8_t* activ
 TG_API int tg_search_states(TgEngine* e, void* states);
 /* canonical serialisation of game g's whole tree, depth-first in child order, one record per
  * initialised node: {move u16, n_children u16, visits u32, virtual u32, result u32,
- * prior f32 bits, q f32 bits}.  Returns record count through *n_records (cap = capacity). */
+ * prior f32 bits, q f32 bits}.  result: TG_ONGOING, the TgResult of a finished position, or under TG_PROOF_ON a TgProven
+ * code.  Returns record count through *n_records (cap = capacity). */
 typedef struct TgNodeRecord {
     uint16_t move;
     uint16_t n_children;

@@ -17,6 +17,7 @@ pub struct SelfPlaySettings {
     pub boost_plies: i32,   // QUAD_ROLLOUT_PLIES (10 in the reference's self_play): moves below this ply get boost_factor × rollouts; 0 = off
     pub boost_factor: i32,  // 4 in the reference's self_play; 1 = off
     pub symmetry: i32,      // sys::TG_SYMM_HASHED: every evaluated leaf goes to the network as a hashed dihedral image (no counterpart in the reference); TG_SYMM_OFF = off
+    pub proof: i32,         // sys::TG_PROOF_ON: proven values in the tree and the proof-aware pick (tg_search_set_proof; no counterpart in the reference); TG_PROOF_OFF = off
     pub noise_alpha: f32,
     pub noise_ratio: f32,
     pub noise_plies: i32,
@@ -38,6 +39,7 @@ impl Default for SelfPlaySettings {
             boost_plies: 0,
             boost_factor: 1,
             symmetry: sys::TG_SYMM_OFF,
+            proof: sys::TG_PROOF_OFF,
             noise_alpha: 0.2,
             noise_ratio: 0.3,
             noise_plies: 80,
@@ -112,6 +114,9 @@ pub fn self_play_with_report<const N: usize>(network: &GpuNet<N>, s: SelfPlaySet
     }
     if s.symmetry != sys::TG_SYMM_OFF {
         check(unsafe { sys::tg_search_set_symmetry(network.e, s.symmetry) })?;
+    }
+    if s.proof != sys::TG_PROOF_OFF {
+        check(unsafe { sys::tg_search_set_proof(network.e, s.proof) })?;
     }
     let mut file = s.example_dir.map(|d| File::create(format!("{d}/{}.data", sys_time())).unwrap()); // self_play.rs:98
     let sb = pack::state_bytes(N);

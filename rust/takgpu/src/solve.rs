@@ -100,4 +100,27 @@ impl<const N: usize> GpuNet<N> {
         })?;
         Ok(a.unpack::<N>())
     }
+
+    /// tg_search_set_proof: `sys::TG_PROOF_ON` / `TG_PROOF_OFF` for the engine's live search / self-play object — proven values
+    /// inside the tree (the MCTS-solver backup; takgpu.h states the rule).  Sticky until the next create.
+    pub fn search_set_proof(&self, mode: i32) -> Result<(), crate::TgError> {
+        check(unsafe { sys::tg_search_set_proof(self.e, mode) })
+    }
+
+    /// tg_search_get_proof: (mode, nodes proven, rollouts that ended on a proven node) since the search was created
+    pub fn search_get_proof(&self) -> Result<(i32, u64, u64), crate::TgError> {
+        let (mut mode, mut proven, mut ended) = (0i32, 0u64, 0u64);
+        check(unsafe { sys::tg_search_get_proof(self.e, &mut mode, &mut proven, &mut ended) })?;
+        Ok((mode, proven, ended))
+    }
+
+    /// tg_search_proof: per game the result code of the root and of each of its children in `possible_moves` order (0, a
+    /// TgResult or a `sys::TG_PROVEN_*` code)
+    pub fn search_proof(&self, games: usize) -> Result<Vec<(u8, Vec<u8>)>, crate::TgError> {
+        let mut root = vec![0u8; games];
+        let mut child = vec![0u8; games * pack::MAX_MOVES];
+        let mut counts = vec![0i32; games];
+        check(unsafe { sys::tg_search_proof(self.e, root.as_mut_ptr(), child.as_mut_ptr(), counts.as_mut_ptr()) })?;
+        Ok((0..games).map(|g| (root[g], child[g * pack::MAX_MOVES..g * pack::MAX_MOVES + counts[g] as usize].to_vec())).collect())
+    }
 }

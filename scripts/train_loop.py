@@ -64,6 +64,8 @@ def parse_args(argv=None):
     ap.add_argument("--symmetry", choices=("off", "hashed"), default="off", help="hashed: self-play and the pit send every leaf to the "
                     "network as a pseudo-random dihedral image (tg_search_set_symmetry); with --holdout the report also carries the "
                     "network's distance from equivariance")
+    ap.add_argument("--proof", choices=("off", "on"), default="off", help="on: self-play keeps proven values in its trees and picks "
+                    "its moves proof-aware (tg_search_set_proof); the pit is not affected")
     ap.add_argument("--window", type=int, default=0, help="> 0: keep the latest N examples in a window on the device and train on all of "
                     "it every round (MAX_EXAMPLES, train/src/main.rs:26: 400000); 0 = train on the fresh harvest only")
     args = ap.parse_args(argv)
@@ -108,7 +110,7 @@ def main():
         old = tak_amd.Engine(args.board, res_blocks=args.blocks, filters=args.filters, evaluator=tak_amd.EVAL_RESNET,
                              max_batch=2 * args.pit_pairs * args.pit_batch)
         old.load_state_dict(tensors)
-    schedule = dict(boost_plies=args.boost_plies, boost_factor=args.boost_factor, symmetry=args.symmetry)
+    schedule = dict(boost_plies=args.boost_plies, boost_factor=args.boost_factor, symmetry=args.symmetry, proof=args.proof)
     eng.selfplay_create(args.games, arena_nodes=1 << 13, seed=0, rollouts=args.rollouts, max_examples=4 * harvest,
                         slot_base=tdist.slot_base(rank, args.games), **schedule)
     report = []

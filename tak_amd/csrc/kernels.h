@@ -240,6 +240,12 @@ void launch_sp_pick(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, in
 // (search_list_kernels.hip) the ascending list of the games owed a ply's boosted iterations, and their count
 void launch_sp_boost_list(hipStream_t st, const SearchDev& S, int boost_plies, int32_t* list, int32_t* count);
 void launch_sp_count_ply(hipStream_t st, const SelfPlayDev& P);
+// search_proof_kernels.hip (TG_PROOF_ON): the selects with the solver backup — list = null: over S.G games and the mask, else over
+// the compacted list —, the roots' statuses for tg_search_proof, the proof-aware pick of self-play
+void launch_select_proof(hipStream_t st, const SearchDev& S, const uint8_t* active, const int32_t* list, int count);
+void launch_backup_select_proof(hipStream_t st, const SearchDev& S, const int32_t* list, int count);
+void launch_proof_read(hipStream_t st, const SearchDev& S, uint8_t* root_status, uint8_t* child_status, int32_t* counts);
+void launch_sp_pick_proof(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, int32_t* op);
 
 // symm_kernels.hip: the dihedral symmetries at the evaluation (tg_policy_eval_symm) and in the search (TG_SYMM_HASHED)
 // perm[8][P]: perm[s][j] = policy slot of the image under s of the move whose slot is j; the caller fills it with −1 first

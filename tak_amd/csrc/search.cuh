@@ -29,7 +29,7 @@ struct NodeHot {
 struct NodeCold {
     uint32_t child;   // pool index of the first child (0 = no children; chunk 0 is never handed out)
     uint16_t mv;      // move that leads here (TgMove)
-    uint16_t nres;    // n_children (12 bits) | TgResult << 12
+    uint16_t nres;    // n_children (12 bits) | TgResult or TgProven << 12
 };
 static_assert(sizeof(NodeHot) == 16 && sizeof(NodeCold) == 8, "node records");
 
@@ -101,7 +101,8 @@ struct SearchDev {
     const int16_t* lut5;
     uint32_t* err;       // error flag word
     unsigned long long* counters;  // [G][2] per game: expansions, evals (summed on read; a single shared word would
-                                   // serialise 2·G same-address atomics per iteration, ≈ 11 ns each)
+                                   // serialise 2·G same-address atomics per iteration, ≈ 11 ns each); behind them [G][2] per
+                                   // game: nodes proven, rollouts that ended on a proven node (TG_PROOF_ON, tree_pass.cuh)
     int G, n, cin_pad, P, ctab_size, legacy5, evaluator;
     int batch, pass;     // virtual rollouts per tree and iteration; the one this launch performs (leaf slot = g·batch + pass)
     int retire;          // 1 = a game past a capacity is retired on its own (self-play); 0 = sticky engine error (caller-driven search)

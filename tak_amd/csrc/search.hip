@@ -158,7 +158,7 @@ int search_alloc(TgEngine* e, const TgSearchConfig* cfg, size_t tree_growth) {
     TG_HIP(bind(s->active, x.active, G));
     TG_HIP(bind(s->noise, x.noise, G * EX_MOVES));
     TG_HIP(bind(s->err, d.err, 1));
-    TG_HIP(bind(s->counters, d.counters, G * 2));
+    TG_HIP(bind(s->counters, d.counters, G * 4));  // (the second half: the proof counters)
     TG_HIP(bind(s->r_moves, x.r_moves, G * EX_MOVES));
     TG_HIP(bind(s->r_visits, x.r_visits, G * EX_MOVES));
     TG_HIP(bind(s->r_prior, x.r_prior, G * EX_MOVES));
@@ -188,7 +188,7 @@ int search_alloc(TgEngine* e, const TgSearchConfig* cfg, size_t tree_growth) {
     TG_HIP(bind(s->ctab, d.ctab, (size_t)ctab_size));
     TG_HIP(hipMemcpy(s->ctab.p, ctab.data(), (size_t)ctab_size * 4, hipMemcpyHostToDevice));
     TG_HIP(hipMemsetAsync(s->err.p, 0, 4, e->stream));
-    TG_HIP(hipMemsetAsync(s->counters.p, 0, G * 16, e->stream));
+    TG_HIP(hipMemsetAsync(s->counters.p, 0, G * 32, e->stream));
     TG_HIP(hipMemsetAsync(s->generation.p, 0, G * 4, e->stream));
     TG_HIP(hipMemsetAsync(s->alive.p, 0, G, e->stream));
     TG_HIP(hipMemsetAsync(s->abort.p, 0, G, e->stream));
@@ -260,12 +260,14 @@ struct GatherScope {
 //   list given:      the same over the compacted list of `count` games (0 < count < G): wave w serves list[w], leaf slots
 //                    w·batch + pass, the network on count × batch leaves
 //   TG_SYMM_HASHED:  one more kernel in front of every `net` (k_symm_leaves over the iteration's leaf slots); off: none
+//   TG_PROOF_ON:     the same schedule with the selects of search_proof_kernels.hip; the backups are the same kernels
 int search_iterate(TgEngine* e, int iters, const uint8_t* d_active, const int32_t* list, int count) {
     Search* s = e->search;
     if (iters <= 0 || (list && count <= 0)) return TG_OK;
     const int leaves = (list ? count : s->d.G) * s->d.batch;
     bind_logits(e, leaves);
     GatherScope scope{e};
+    if (s->proof) s->proof_ran = true;
     SearchDev d = s->d;
     d.pass = d.batch > 1 ? -1 : 0;  // -1: the kernel runs the `batch` passes of a game back to back in that game's wave
     hipStream_t st = e->stream;
@@ -277,7 +279,8 @@ int search_iterate(TgEngine* e, int iters, const uint8_t* d_active, const int32_
     }
     for (int i = 0; i < iters; i++) {
         if (i == 0 || d_active) {
-            if (list) launch_select_list(st, d, list, count);
+            if (s->proof) launch_select_proof(st, d, d_active, list, count);
+            else if (list) launch_select_list(st, d, list, count);
             else launch_select(st, d, d_active);
         }
         if (e->cfg.evaluator == TG_EVAL_RESNET) {
@@ -287,7 +290,8 @@ int search_iterate(TgEngine* e, int iters, const uint8_t* d_active, const int32_
             if (rc) return rc;
         }
         const bool last = d_active || i + 1 == iters;  // (nothing follows, or the next select needs the mask)
-        if (list) last ? launch_backup_list(st, d, list, count) : launch_backup_select_list(st, d, list, count);
+        if (!last && s->proof) launch_backup_select_proof(st, d, list, count);
+        else if (list) last ? launch_backup_list(st, d, list, count) : launch_backup_select_list(st, d, list, count);
         else last ? launch_backup(st, d) : launch_backup_select(st, d);
     }
     TG_HIP(hipGetLastError());
@@ -340,6 +344,7 @@ int tg_search_reset(TgEngine* e, const void* states) {
     TG_HIP(hipMemcpyAsync(s->root_state.p, states, G * e->g.bytes, hipMemcpyHostToDevice, e->stream));
     TG_HIP(hipMemsetAsync(s->alive.p, 1, G, e->stream));
     TG_HIP(hipMemsetAsync(s->err.p, 0, 4, e->stream));
+    s->proof_ran = false;
     return search_reset_trees(e);
 }
 
@@ -566,6 +571,58 @@ int tg_search_counters(TgEngine* e, uint64_t* expansions, uint64_t* evals) {
     if (rc) return rc;
     if (expansions) *expansions = c[0];
     if (evals) *evals = c[1];
+    return TG_OK;
+}
+
+int tg_search_set_proof(TgEngine* e, int mode) {
+    if (!e) return fail(TG_ERR_INVALID_ARG, "tg_search_set_proof: null engine");
+    int rc = need_search(e);
+    if (rc) return rc;
+    if (mode != TG_PROOF_OFF && mode != TG_PROOF_ON) return fail(TG_ERR_INVALID_ARG, "tg_search_set_proof: unknown mode");
+    // the rollouts of the off mode know the TgResult codes alone: they would back a proven node up as a draw
+    if (mode == TG_PROOF_OFF && e->search->proof != TG_PROOF_OFF && e->search->proof_ran)
+        return fail(TG_ERR_STATE, "tg_search_set_proof: iterations have run under TG_PROOF_ON since the last tg_search_reset, the trees may hold "
+                                  "proven nodes; TG_PROOF_OFF is accepted in front of the first iteration after a tg_search_reset or a create");
+    e->search->proof = mode;
+    return TG_OK;
+}
+
+int tg_search_get_proof(TgEngine* e, int* mode, uint64_t* nodes_proven, uint64_t* rollouts_ended_on_proven) {
+    if (!e) return fail(TG_ERR_INVALID_ARG, "tg_search_get_proof: null engine");
+    int rc = need_search(e);
+    if (rc) return rc;
+    rc = sync_and_check(e);
+    if (rc) return rc;
+    Search* s = e->search;
+    const size_t G = (size_t)s->d.G;
+    std::vector<unsigned long long> h(G * 2);
+    TG_HIP(hipMemcpy(h.data(), s->d.counters + G * 2, h.size() * 8, hipMemcpyDeviceToHost));
+    unsigned long long a = 0, b = 0;
+    for (size_t g = 0; g < G; g++) { a += h[2 * g]; b += h[2 * g + 1]; }
+    if (mode) *mode = s->proof;
+    if (nodes_proven) *nodes_proven = a;
+    if (rollouts_ended_on_proven) *rollouts_ended_on_proven = b;
+    return TG_OK;
+}
+
+int tg_search_proof(TgEngine* e, uint8_t* root_status, uint8_t* child_status, int32_t* counts) {
+    if (!e) return fail(TG_ERR_INVALID_ARG, "tg_search_proof: null engine");
+    int rc = need_search(e);
+    if (rc) return rc;
+    Search* s = e->search;
+    const size_t G = (size_t)s->d.G;
+    uint8_t *d_root, *d_child;
+    int32_t* d_counts;
+    TG_HIP(bind(s->p_root, d_root, G));
+    TG_HIP(bind(s->p_child, d_child, G * EX_MOVES));
+    TG_HIP(bind(s->p_counts, d_counts, G));
+    launch_proof_read(e->stream, s->d, d_root, d_child, d_counts);
+    TG_HIP(hipGetLastError());
+    rc = sync_and_check(e);
+    if (rc) return rc;
+    TG_HIP(copy_out(root_status, d_root, G));
+    TG_HIP(copy_out(child_status, d_child, G * EX_MOVES));
+    TG_HIP(copy_out(counts, d_counts, G));
     return TG_OK;
 }
 

@@ -40,6 +40,9 @@ struct Search {
     DevBuf st_hdr, st_state, st_moves, st_visits, st_count, out_hdr, out_state, out_moves, out_visits, fin, recycle, out_off, chosen,
         mask, stats;
     unsigned long long drained = 0, dropped = 0;
+    int proof = 0;  // tg_search_set_proof: TG_PROOF_ON = the selects and the self-play pick of search_proof_kernels.hip
+    bool proof_ran = false;  // iterations have run under TG_PROOF_ON since the trees were last reset: they may hold TG_PROVEN_* codes
+    DevBuf p_root, p_child, p_counts;  // tg_search_proof
     // rollout schedule (tg_selfplay_set_schedule): games under boost_plies run boost_factor × rollouts iterations, the extra
     // ones over a compacted list of those games
     TgRolloutSchedule sched{};

@@ -442,25 +442,6 @@ __global__ __launch_bounds__(WPB * 64) void k_sp_opening(SearchDev S) {
     ws_store(s, st, geo);
 }
 
-__device__ inline void stage_example(const SearchDev& S, const SelfPlayDev& P, int g, const WState& s, const Geom& geo,
-                                     uint32_t nmoves, int& slot_out) {
-    // reserves the next staging slot of game g and writes header + state; returns the slot (or -1)
-    int k = P.st_count[g];
-    if (k >= P.max_game_plies) { limit_hit(S, g, ERRF_EXAMPLES); slot_out = -1; return; }
-    size_t e = (size_t)g * P.ex_per_game + k;
-    ws_store(s, P.st_state + e * geo.bytes, geo);
-    if (lane_id() == 0) {
-        ExampleRec h;
-        h.slot = (int32_t)(S.slot_base + (uint32_t)g);
-        h.generation = (int32_t)S.generation[g];
-        h.n_moves = (int32_t)nmoves;
-        h.result = 0.0f;
-        P.st_hdr[e] = h;
-        P.st_count[g] = k + 1;
-    }
-    slot_out = k;
-}
-
 // (b) instant-win scan, :119-171
 __global__ __launch_bounds__(WPB * 64) void k_sp_instant_win(SearchDev S, SelfPlayDev P) {
     __shared__ uint16_t mv_lds[WPB][EX_MOVES];

@@ -2,7 +2,7 @@
 // (select_pass: virtual_rollout + select, mcts.rs:26-65,94-118) and its de-virtualisation (backup_pass: devirtualize_path,
 // mcts.rs:67-91), the node pool's take / give, the wave helpers.  Included by search_kernels.hip (one wave per game, wave → game
 // by identity) and search_list_kernels.hip (wave → game through a compacted list): the same operations on a game's tree in the
-// same order from both, so the trees are the same bit for bit.
+// same order from both, so the trees are the same bit for bit; and by search_proof_kernels.hip, both mappings with PROOF = true.
 #pragma once
 #include <stdlib.h>
 
@@ -91,6 +91,76 @@ __device__ inline void update_concrete(NodeHot& h, float reward) {
     h.q = (cumulative + reward) / (float)h.visits;
 }
 
+// self-play (k_sp_instant_win, k_sp_pick and its proof-aware twin): reserves the next staging slot of game g and writes header +
+// state; returns the slot (or -1)
+__device__ inline void stage_example(const SearchDev& S, const SelfPlayDev& P, int g, const WState& s, const Geom& geo,
+                                     uint32_t nmoves, int& slot_out) {
+    int k = P.st_count[g];
+    if (k >= P.max_game_plies) { limit_hit(S, g, ERRF_EXAMPLES); slot_out = -1; return; }
+    size_t e = (size_t)g * P.ex_per_game + k;
+    ws_store(s, P.st_state + e * geo.bytes, geo);
+    if (lane_id() == 0) {
+        ExampleRec h;
+        h.slot = (int32_t)(S.slot_base + (uint32_t)g);
+        h.generation = (int32_t)S.generation[g];
+        h.n_moves = (int32_t)nmoves;
+        h.result = 0.0f;
+        P.st_hdr[e] = h;
+        P.st_count[g] = k + 1;
+    }
+    slot_out = k;
+}
+
+// ---- proven values in the tree (the MCTS-solver backup of Winands et al.; no counterpart in the reference) ----
+// status of a node from the result nibble of its cold record: 0 = decided for white, 1 = for black, 2 = a draw, 3 = unknown
+// (ongoing; an uninitialised child's record is 0 = TG_ONGOING)
+constexpr uint32_t PS_DRAW = 2u, PS_UNKNOWN = 3u;
+__device__ inline uint32_t proof_status(uint32_t r) {
+    return (r == TG_WHITE_ROAD || r == TG_WHITE_FLAT || r == TG_PROVEN_WHITE) ? 0u
+         : (r == TG_BLACK_ROAD || r == TG_BLACK_FLAT || r == TG_PROVEN_BLACK) ? 1u
+         : (r == TG_DRAW || r == TG_DRAW_REVERSIBLE || r == TG_PROVEN_DRAW) ? PS_DRAW : PS_UNKNOWN;
+}
+// The rule, for an initialised ongoing node X whose side to move has colour c: some child decided for c → X is TG_PROVEN_c;
+// else no child unknown → TG_PROVEN_DRAW if some child is a draw, TG_PROVEN_(opponent of c) otherwise; else nothing.
+// Called by the whole wave of game g behind the unwind of a rollout that has just initialised the terminal node at depth `depth`
+// (path[d - 1] = the node at depth d, in LDS) with result `res`: walks upward from the leaf's parent.  A child decided for
+// the parent's mover decides the parent without a scan; otherwise one lane-strided scan of the parent's children block (cold
+// records only).  Stops at the first level that stays unknown.  The parent keeps its child count and its children.
+__device__ inline void proof_walk(const SearchDev& S, const int g, const uint32_t root, const uint32_t root_color,
+                                  const uint32_t* path, const int depth, const uint32_t res) {
+    const int lane = lane_id();
+    NodeCold* cold = S.cold;
+    uint32_t cst = proof_status(res);  // wave-uniform: status of the child the walk comes from
+    uint32_t proven = 0;
+    wave_sync_mem();  // the leaf's record was written by lane 0; the scans below read it from every lane
+    for (int d = depth - 1; d >= 0 && cst != PS_UNKNOWN; d--) {
+        const uint32_t x = uni(d == 0 ? root : path[d - 1]);
+        const uint32_t c = root_color ^ (uint32_t)(d & 1);
+        const NodeCold xc = cold[x];
+        const uint32_t xn = uni((uint32_t)xc.nres), xb = uni(xc.child);
+        if ((xn >> 12) != TG_ONGOING) break;  // (cannot be: the descent went through it)
+        uint32_t code = 0;
+        if (cst == c) code = c == 0 ? TG_PROVEN_WHITE : TG_PROVEN_BLACK;
+        else {
+            const uint32_t nchild = xn & 0xfffu;
+            bool unk = false, win = false, drw = false;
+            for (uint32_t i = lane; i < nchild; i += 64) {
+                const uint32_t st = proof_status((uint32_t)cold[xb + i].nres >> 12);
+                unk |= st == PS_UNKNOWN; win |= st == c; drw |= st == PS_DRAW;
+            }
+            if (__ballot(win)) code = c == 0 ? TG_PROVEN_WHITE : TG_PROVEN_BLACK;
+            else if (!__ballot(unk)) code = __ballot(drw) ? TG_PROVEN_DRAW : (c == 0 ? TG_PROVEN_BLACK : TG_PROVEN_WHITE);
+        }
+        if (code == 0) break;
+        if (lane == 0) cold[x].nres = (uint16_t)((xn & 0xfffu) | (code << 12));
+        proven++;
+        cst = proof_status(code);
+        wave_sync_mem();  // the next level's scan reads this record
+    }
+    if (proven && lane == 0)
+        __hip_atomic_fetch_add(&S.counters[2 * (size_t)S.G + 2 * (size_t)g], (unsigned long long)proven, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ------------------------------------------------------------------------------------------------
 // virtual_rollout (+ select): descend, expand the first uninitialised node, mark the path with a
 // virtual visit (or back a concrete result up when the rollout ends on a terminal node), and leave
@@ -112,7 +182,10 @@ struct RootPre {
 
 // LIST: the wave serves an entry of a compacted list of games (the k_*_list kernels below): everything of the tree and the game
 // is game g's, the leaf slot is the LIST POSITION w's — w·batch + p — so that the network sees a dense batch of the listed games.
-template <int NB, bool LIST = false>
+// PROOF: the MCTS-solver backup (tg_search_set_proof, search_proof_kernels.hip): a rollout that has just initialised a terminal
+// node draws the conclusion for its ancestors (proof_walk above), a rollout that ends on a proven node backs its colour up like
+// a terminal's.  false: none of it is compiled.
+template <int NB, bool LIST = false, bool PROOF = false>
 __device__ __forceinline__ void select_pass(const SearchDev& S, const uint8_t* __restrict__ active, const int g, const int pass,
                                             uint32_t* path, uint16_t* mvl, const RootPre& pre = RootPre(), const int w = 0) {
     const int lane = lane_id();
@@ -143,6 +216,7 @@ __device__ __forceinline__ void select_pass(const SearchDev& S, const uint8_t* _
     int depth = 0;
     uint32_t res = TG_ONGOING;
     bool terminal = false;
+    bool fresh = false;  // (PROOF) the rollout ended by initialising its node, not on a known one
 
     // The (visits, virtual, child, n|result) of the node being visited travel in registers: they are read
     // once for the root and afterwards come out of the children scan of the level above, so each level
@@ -238,6 +312,7 @@ __device__ __forceinline__ void select_pass(const SearchDev& S, const uint8_t* _
                 S.leaf_rec[2 * slot + 1] = count;
             }
             terminal = res != TG_ONGOING;
+            fresh = true;
             TG_TSTAMP(g, 27);  // children created
             break;
         }
@@ -325,8 +400,8 @@ __device__ __forceinline__ void select_pass(const SearchDev& S, const uint8_t* _
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
     // ---- unwind (mcts.rs:55-62): lane d handles the node at depth d ----
-    const bool winner = res >= TG_WHITE_ROAD && res <= TG_BLACK_FLAT;
-    const uint32_t wcolor = (res == TG_WHITE_ROAD || res == TG_WHITE_FLAT) ? 0u : 1u;
+    const bool winner = (res >= TG_WHITE_ROAD && res <= TG_BLACK_FLAT) || (PROOF && (res == TG_PROVEN_WHITE || res == TG_PROVEN_BLACK));
+    const uint32_t wcolor = (res == TG_WHITE_ROAD || res == TG_WHITE_FLAT || (PROOF && res == TG_PROVEN_WHITE)) ? 0u : 1u;
     for (int d = lane; d <= depth; d += 64) {
         uint32_t nd = d == 0 ? root : path[d - 1];
         if (!terminal && S.batch == 1) {
@@ -347,6 +422,11 @@ __device__ __forceinline__ void select_pass(const SearchDev& S, const uint8_t* _
         }
     }
     TG_TSTAMP(g, 28);  // virtual visits marked
+    if constexpr (PROOF) {
+        if (terminal && fresh) proof_walk(S, g, root, root_color, path, depth, res);
+        else if (terminal && res >= TG_PROVEN_WHITE && lane == 0)  // the descent ended on a proven node
+            __hip_atomic_fetch_add(&S.counters[2 * (size_t)S.G + 2 * (size_t)g + 1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     uint32_t* gpath = S.path + slot * MAX_DEPTH;
     for (int d = lane; d < depth; d += 64) gpath[d] = path[d];
     if (!terminal) {

@@ -147,6 +147,7 @@ ABI_SYMBOLS = [
     "tg_policy_eval_symm", "tg_policy_eval_symm_dev", "tg_symm_perm_read", "tg_search_set_symmetry", "tg_search_get_symmetry",
     "tg_search_create", "tg_search_reset", "tg_search_run", "tg_search_apply_dirichlet", "tg_search_apply_noise",
     "tg_search_root", "tg_search_play", "tg_search_states", "tg_search_dump", "tg_search_debug", "tg_search_counters", "tg_search_pool",
+    "tg_search_set_proof", "tg_search_get_proof", "tg_search_proof",
     "tg_solve", "tg_search_solve",
     "tg_selfplay_create", "tg_selfplay_step", "tg_selfplay_stats", "tg_selfplay_drain",
     "tg_selfplay_set_schedule", "tg_selfplay_schedule_stats",
@@ -169,6 +170,26 @@ def _symmetry_mode(mode):
             raise ValueError(f"symmetry must be 'off' or 'hashed', not {mode!r}")
         return SYMM_HASHED if mode == "hashed" else SYMM_OFF
     return int(mode)
+
+
+PROOF_OFF, PROOF_ON = 0, 1  # TgSearchProof
+PROVEN_WHITE, PROVEN_BLACK, PROVEN_DRAW = 8, 9, 10  # TgProven: node-record codes beside the TgResult ones
+STATUS_WHITE, STATUS_BLACK, STATUS_DRAW, STATUS_UNKNOWN = 0, 1, 2, 3
+_STATUS_OF_CODE = np.array([3, 0, 0, 1, 1, 2, 2, 3, 0, 1, 2, 3, 3, 3, 3, 3], np.uint8)
+
+
+def node_status(codes):
+    """STATUS_* of result codes (TgNodeRecord.result, Engine.search_proof): white for a white win or TG_PROVEN_WHITE, black
+    likewise, draw for both draws and TG_PROVEN_DRAW, unknown otherwise (include/takgpu.h)"""
+    return _STATUS_OF_CODE[np.asarray(codes, np.int64) & 15]
+
+
+def _proof_mode(mode):
+    if isinstance(mode, str):
+        if mode not in ("off", "on"):
+            raise ValueError(f"proof must be 'off' or 'on', not {mode!r}")
+        return PROOF_ON if mode == "on" else PROOF_OFF
+    return int(mode)  # (True / False too)
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -686,6 +707,24 @@ class Engine:
         self._check(self.lib.tg_search_get_symmetry(self.h, C.byref(mode), C.byref(count)))
         return mode.value, count.value
 
+    def search_set_proof(self, mode):
+        """tg_search_set_proof: PROOF_OFF / PROOF_ON (or "off" / "on", False / True) for the current search or self-play object"""
+        self._check(self.lib.tg_search_set_proof(self.h, _proof_mode(mode)))
+
+    def search_get_proof(self):
+        """(mode, nodes proven, rollouts that ended on a proven node) since the search was created; synchronises"""
+        mode, a, b = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.tg_search_get_proof(self.h, C.byref(mode), C.byref(a), C.byref(b)))
+        return mode.value, a.value, b.value
+
+    def search_proof(self):
+        """tg_search_proof: dict(root_status [games], child_status [games, TG_MAX_MOVES], counts [games]) — the result code of every
+        root and of its children in possible_moves order (0, a TgResult or a TG_PROVEN_* code; node_status maps them)"""
+        g = self.games
+        o = dict(root_status=np.zeros(g, np.uint8), child_status=np.zeros((g, TG_MAX_MOVES), np.uint8), counts=np.zeros(g, np.int32))
+        self._check(self.lib.tg_search_proof(self.h, _p(o["root_status"]), _p(o["child_status"]), _p(o["counts"])))
+        return o
+
     def forward_mcts(self, planes):
         planes = np.ascontiguousarray(planes, np.float32).reshape(-1, self.cin, self.n, self.n)
         k = planes.shape[0]
@@ -698,14 +737,18 @@ class Engine:
         self._check(self.lib.tg_policy_eval_dev(self.h, n, C.c_void_p(d_states), C.c_void_p(d_policy), C.c_void_p(d_eval)))
 
     # ---- Node / search ----------------------------------------------------------------------------
-    def search_create(self, games, arena_nodes=1 << 16, base=500.0, init=4.0, seed=0, slot_base=0, batch=1, visit_limit=0, symmetry=None):
+    def search_create(self, games, arena_nodes=1 << 16, base=500.0, init=4.0, seed=0, slot_base=0, batch=1, visit_limit=0, symmetry=None,
+                      proof=None):
         """batch: virtual rollouts per tree and iteration (Player's batching); games * batch <= max_batch
+        proof: PROOF_ON / "on" / True = proven values in the tree (search_set_proof); None = off
         symmetry: SYMM_HASHED / "hashed" = one hashed dihedral image per evaluated leaf (search_set_symmetry); None = off"""
         cfg = TgSearchConfig(games, arena_nodes, base, init, seed, slot_base, batch, visit_limit, 0)
         self._check(self.lib.tg_search_create(self.h, C.byref(cfg)))
         self.games = games
         if symmetry is not None and _symmetry_mode(symmetry) != SYMM_OFF:
             self.search_set_symmetry(symmetry)
+        if proof is not None and _proof_mode(proof) != PROOF_OFF:
+            self.search_set_proof(proof)
 
     def search_reset(self, states):
         states, k = self._states(states)
@@ -829,8 +872,10 @@ class Engine:
     # ---- self_play_parallel ------------------------------------------------------------------------
     def selfplay_create(self, games, arena_nodes=0, base=500.0, init=4.0, seed=0, rollouts=400, noise_plies=80,
                         exploit_plies=40, noise_alpha=0.2, noise_ratio=0.3, komi=2, total_games=0, max_examples=1 << 16,
-                        slot_base=0, max_game_plies=0, visit_limit=0, batch=1, boost_plies=0, boost_factor=1, symmetry=None):
-        """batch: virtual rollouts per game and iteration (Player's batching; the reference's self_play uses 32): `rollouts`
+                        slot_base=0, max_game_plies=0, visit_limit=0, batch=1, boost_plies=0, boost_factor=1, symmetry=None,
+                        proof=None):
+        """proof: PROOF_ON / "on" / True = proven values in the tree and the proof-aware pick (search_set_proof); None = off
+        batch: virtual rollouts per game and iteration (Player's batching; the reference's self_play uses 32): `rollouts`
         iterations of `batch` rollouts per move, games * batch leaves per network call, games * batch <= max_batch
         boost_plies, boost_factor: the rollout schedule (QUAD_ROLLOUT_PLIES; the reference's self_play uses 10 and 4): a move
         of a game whose ply < boost_plies gets boost_factor * rollouts iterations.  0 / 1 = off: the setter is not called"""
@@ -843,6 +888,8 @@ class Engine:
             self.selfplay_set_schedule(boost_plies, boost_factor)
         if symmetry is not None and _symmetry_mode(symmetry) != SYMM_OFF:  # (None / off: the setter is not called)
             self.search_set_symmetry(symmetry)
+        if proof is not None and _proof_mode(proof) != PROOF_OFF:
+            self.search_set_proof(proof)
 
     def selfplay_set_schedule(self, boost_plies, boost_factor, reserved=(0, 0)):
         """tg_selfplay_set_schedule as it is: after selfplay_create, before the first selfplay_step"""

@@ -9,7 +9,7 @@ Players can share one engine only one at a time (the engine holds one search sta
 import numpy as np
 
 from .analysis import MAX_BRANCH_LENGTH, Analysis, NodeDebugInfo, root_eval
-from .engine import TG_MAX_MOVES
+from .engine import TG_MAX_MOVES, node_status
 
 # node_budget of a Player's solver calls.  The library's default (2^10) is sized so that a launch over thousands of positions stays
 # short on a shared card; it cannot finish the proof of a loss two plies deep (every reply × every answer: ≈ 60² positions).  A
@@ -20,16 +20,19 @@ TACTICS_BUDGET = 1 << 16
 
 class Player:
     def __init__(self, engine, batch, save_examples, game, arena_nodes=1 << 16, seed=0, create_analysis=False, symmetry=None, tactics=0,
-                 tactics_budget=TACTICS_BUDGET):
+                 tactics_budget=TACTICS_BUDGET, proof=None):
         """Player::new(network, batch, save_examples, create_analysis, &game); `game` is a packed state.
         symmetry: "hashed" / SYMM_HASHED = every evaluated leaf goes to the network as a hashed dihedral image (Engine.search_set_symmetry)
         tactics: D > 0 = the analysis annotates every played move that has info with the forced-win solver at depth D (Analysis.annotate_tactics);
         0 (default) = no solver call anywhere
-        tactics_budget: node_budget of this player's solver calls (pick_move's and the annotation's)"""
+        tactics_budget: node_budget of this player's solver calls (pick_move's and the annotation's)
+        proof: "on" / PROOF_ON / True = proven values in the tree (Engine.search_set_proof) and the proof-aware pick_move"""
         self.e = engine
         self.tactics = int(tactics)
         self.tactics_budget = int(tactics_budget)
         self.last_tactics = None  # the Engine.search_solve result of the last pick_move(…, tactics > 0)
+        self.proof = proof is not None and proof not in (0, False, "off")
+        self.last_proof = None  # with proof: the Engine.search_proof result of the last pick_move
         self.batch = int(batch)
         self.save_examples = bool(save_examples)
         self.create_analysis = bool(create_analysis)
@@ -39,7 +42,7 @@ class Player:
         hdr = game[engine.sb - 16:]
         self.analysis = Analysis(engine.n, int(hdr[8:9].view(np.int8)[0]), int(hdr[2:4].view("<u2")[0]))
         self.rng = np.random.default_rng(seed)
-        engine.search_create(1, arena_nodes=arena_nodes, seed=seed, batch=self.batch, symmetry=symmetry)
+        engine.search_create(1, arena_nodes=arena_nodes, seed=seed, batch=self.batch, symmetry=symmetry, proof=proof)
         engine.search_reset(np.ascontiguousarray(game, np.uint8).reshape(1, -1))
         self.rollout()  # the reference requests the first batch in the constructor (player.rs:65-66)
 
@@ -63,10 +66,19 @@ class Player:
     def pick_move(self, exploitation, tactics=0):
         """Node::pick_move (play.rs:49-67): most visited (last on ties) or sampled ∝ visits.
         tactics = D > 0: first solve the root at depth D (Engine.search_solve).  A proven win returns its `best` move; otherwise
-        the moves with a proven loss leave the candidates (unless every move is one).  0: no solver call, the reference's pick."""
+        the moves with a proven loss leave the candidates (unless every move is one).  0: no solver call, the reference's pick.
+        With proof (after the tactics step, on what it left): a move into a position the tree has decided for the mover is played —
+        the most visited such move, the last on ties, whatever `exploitation`; otherwise the moves decided for the opponent leave
+        the candidates (unless every move is one), and candidates without any visit are picked from by exploitation."""
         moves, visits = self.improved_policy()
         if len(moves) == 0:
             raise RuntimeError("pick_move on a root without children")
+        status = None
+        if self.proof:
+            p = self.last_proof = self.e.search_proof()
+            if int(p["counts"][0]) != len(moves):
+                raise RuntimeError("pick_move: the root's children are not the proof's status list")
+            status = node_status(p["child_status"][0, : len(moves)])
         if tactics > 0:
             r = self.last_tactics = self.e.search_solve(int(tactics), node_budget=self.tactics_budget)
             if int(r["value"][0]) > 0:
@@ -77,6 +89,17 @@ class Player:
             keep = r["move_values"][0, :c] >= 0
             if keep.any():
                 moves, visits = moves[keep], visits[keep]
+                status = status[keep] if status is not None else None
+        if status is not None:
+            mover = int(self.state()[self.e.sb - 16 + 1])
+            mine = status == mover
+            if mine.any():
+                moves, visits = moves[mine], visits[mine]
+                return int(moves[len(visits) - 1 - int(np.argmax(visits[::-1]))])
+            keep = status != (mover ^ 1)
+            if keep.any():
+                moves, visits = moves[keep], visits[keep]
+            exploitation = exploitation or int(visits.sum()) == 0
         if exploitation:
             return int(moves[len(visits) - 1 - int(np.argmax(visits[::-1]))])
         total = int(visits.sum())
