@@ -823,6 +823,59 @@ TG_API int tg_window_read(TgEngine* e, int first, int n, TgExampleHeader* header
 TG_API int tg_window_train(TgEngine* e, int first, int count, uint64_t seed, float* mean_loss_p, float* mean_loss_z, int32_t* steps);
 
 /* ---------------------------------------------------------------------------------------
+ * Reanalyse: refresh the policy targets of window rows by search, on the device.  No counterpart in the reference:
+ * training_loop trains on the whole window each round (train/src/main.rs:82-95), and every row keeps the visit counts
+ * (Node::improved_policy, alpha-tak/src/search/play.rs:13-21) of the search that produced it, so in a long run most rows carry
+ * the targets of networks many generations old.  tg_reanalyse searches the positions of logical rows [first, first + count)
+ * again with the network the engine holds now and writes the new root visit counts into the rows in place (MuZero's Reanalyse,
+ * restricted to the policy target).  Off unless called.
+ * Search object: the call runs on the engine's live caller-driven search object (tg_search_create) and takes from it the
+ * number of slots (`games`) and `batch`, the exploration constants, the seed, the arena, and the sticky modes of
+ * tg_search_set_symmetry and tg_search_set_proof.  It DESTROYS that object's trees: afterwards the object holds the trees of
+ * the last slice, and the caller resets it (tg_search_reset) before using it again.
+ * Slices: the rows are processed `games` at a time.  For each slice (1) every slot's root state is copied from its row on the
+ * device and its tree becomes Node::default(); the slots beyond a short last slice are dead, as retired self-play slots, and
+ * cost nothing in the tree kernels; (2) with noise_alpha > 0: one iteration, then Node::apply_dirichlet(noise_alpha,
+ * noise_ratio) — Player::add_noise's order, as the self-play driver; (3) `rollouts` iterations of `batch` virtual rollouts, the
+ * schedule of tg_search_run without a mask (TG_SYMM_HASHED and TG_PROOF_ON honoured); (4) a row's visits are overwritten only
+ * if the root's child count equals the row's n_moves, every child's move equals the row's move at the same index, and the
+ * children's visits sum to more than 0: then visits[i] = the real visit count of child i and the entries past n_moves stay
+ * zero (the row stays canonical).  Otherwise the row is left byte for byte as it was and counted as `mismatched`
+ * (tg_window_push does not check that a pushed move list is possible_moves; a finished position has no children) or as
+ * `unvisited` (under TG_PROOF_ON a proven root collects no visits).  State, moves, n_moves, result and game_id of a row are
+ * never written, and no row outside the range is.
+ * Noise key: the k-th example that ever entered the window is at cursor k, logical index i is cursor TgWindowInfo.evicted + i,
+ * and for the duration of a slice the object's slot_base is the low 32 bits of its first row's cursor.  A row's noise is
+ * gamma_sample(alpha, seed, (uint32_t)cursor, generation 0, ply, i): a function of the row and the seed, whatever `games` is
+ * and however the range was sliced.  The object's own slot_base is back in place when the call returns.
+ * Determinism: without noise a row's new visits depend on its state, the network, the search configuration and the seed
+ * only — not on `games`, the slicing or the row's neighbours.
+ * Errors: a null engine or cfg, first or count negative, a range outside [0, TgWindowInfo.count], rollouts < 1,
+ * noise_alpha < 0, noise_ratio outside [0, 1], flags or a reserved field not 0 -> TG_ERR_INVALID_ARG naming the field; no
+ * window, no search object, or a self-play object (its games would be destroyed) -> TG_ERR_STATE.  After any of these the
+ * window and the search are untouched.  count = 0 -> TG_OK, zero stats.  A search error in the middle
+ * (TG_ERR_ARENA_OVERFLOW, TG_ERR_LIMIT, TG_ERR_NAN) is returned: the slices stored before it keep their new visits, the
+ * failing slice and those behind it are unchanged, and *out counts what was stored.
+ * Host traffic: synchronises before it returns (and once per slice, for the error word).  Only lengths, flags and counters
+ * reach the host: no state, move or visit of a row does.
+ * ------------------------------------------------------------------------------------- */
+typedef struct TgReanalyseConfig {
+    int32_t rollouts;     /* search iterations per row (each `batch` virtual rollouts of the search object); >= 1 */
+    float noise_alpha;    /* 0 = no Dirichlet noise */
+    float noise_ratio;
+    uint32_t flags;       /* must be 0 */
+    int32_t reserved[4];  /* must be 0 */
+} TgReanalyseConfig;      /* 32 bytes */
+typedef struct TgReanalyseStats {
+    uint64_t rows;        /* count */
+    uint64_t updated;     /* rows whose visits were rewritten */
+    uint64_t mismatched;  /* rows left as they were: root's children != the row's move list (count or any move) */
+    uint64_t unvisited;   /* rows left as they were: no root child got a visit */
+    uint64_t expansions, evals;  /* the search counters' growth over the call */
+} TgReanalyseStats;       /* 48 bytes */
+TG_API int tg_reanalyse(TgEngine* e, int first, int count, const TgReanalyseConfig* cfg, TgReanalyseStats* out /* optional */);
+
+/* ---------------------------------------------------------------------------------------
  * Pit (replaces `pit`, train/src/pit.rs:15-96): the new network against the old one,
  * `pairs` openings × both colours, all 2·pairs games concurrently — one engine handle per weight set, each
  * holding one tree per game (the reference gives each side its own `Player`).  The side to move runs `rollouts`

@@ -9,7 +9,8 @@
 //! | `Network::train` — network.rs:37-97                          | [`net::GpuNet::train`], [`dp`]         |
 //! | `self_play_parallel` — train/src/self_play.rs:96-262         | [`selfplay::self_play_parallel_gpu`]   |
 //! | `examples` of `training_loop` — train/src/main.rs:26,56-123 | [`window`]: `GpuNet::window_*`         |
-//! | `pit` — train/src/pit.rs:15-96                               | [`pit::pit_gpu`]                       |
+//! | no counterpart; main.rs:82-95 retrains on old targets        | [`reanalyse`]: `GpuNet::reanalyse`     |
+//! | `pit` — train/src/pit.rs:15-96                              | [`pit::pit_gpu`]                       |
 //! | the instant-win scan — train/src/self_play.rs:118-171, deepened to forced wins | [`solve`]: `GpuNet::solve`  |
 //! | `Game<N>` / `Move` / `Example<N>` — tak/src/game.rs:24-35, takparse, alpha-tak/src/example.rs:29-33 | [`pack`] |
 //!
@@ -19,6 +20,7 @@ pub mod dp;
 pub mod net;
 pub mod pack;
 pub mod pit;
+pub mod reanalyse;
 pub mod selfplay;
 pub mod solve;
 pub mod window;

@@ -14,6 +14,12 @@ device.  Every round's harvest is absorbed from the self-play ring into a window
 the network trains on the whole window (tg_window_train), not on the fresh harvest only; nothing is drained, concatenated or
 uploaded.  With --holdout the newest share of the window is read back (tg_window_read) for tg_eval_examples and kept out by
 training on the range before it; it is trained on from the next round on, when newer examples have taken its place.
+
+--reanalyse-rows N (default 0: the loop as it was; needs --window) refreshes the policy targets of the OLDEST min(N, count) rows of
+the window every round, after the absorb and before the training: tg_reanalyse searches their positions again with the network that
+has just played, --reanalyse-rollouts iterations each (0 = --rollouts), on a search object created for the purpose, and writes
+the new visit counts into the rows on the device.  That object replaces the self-play driver, so self-play is created anew at
+the end of the round, as it is after a pit.
 """
 import argparse
 import json
@@ -68,7 +74,14 @@ def parse_args(argv=None):
                     "its moves proof-aware (tg_search_set_proof); the pit is not affected")
     ap.add_argument("--window", type=int, default=0, help="> 0: keep the latest N examples in a window on the device and train on all of "
                     "it every round (MAX_EXAMPLES, train/src/main.rs:26: 400000); 0 = train on the fresh harvest only")
+    ap.add_argument("--reanalyse-rows", type=int, default=0, help="> 0: every round, search the oldest N rows of the window again with the "
+                    "current network and rewrite their visit counts on the device (tg_reanalyse); needs --window; 0 = off")
+    ap.add_argument("--reanalyse-rollouts", type=int, default=0, help="search iterations per reanalysed row; 0 = --rollouts")
     args = ap.parse_args(argv)
+    if args.reanalyse_rows < 0 or args.reanalyse_rollouts < 0:
+        ap.error("--reanalyse-rows and --reanalyse-rollouts must not be negative")
+    if args.reanalyse_rows and not args.window:
+        ap.error("--reanalyse-rows refreshes rows of the example window: it needs --window")
     if args.window < 0:
         ap.error("--window must be 0 (off) or a number of examples")
     if not 0 <= args.boost_plies <= 512:
@@ -154,6 +167,15 @@ def main():
                 return {"mean_abs_dp": dp / n_p if n_p else None, "mean_abs_dv": dv / n_v if n_v else None}
 
             held_out = {"examples": hold * world, "before": held_means(), "equivariance_before": equivariance()}
+        reanalysed = None
+        if args.reanalyse_rows:
+            # the oldest rows carry the targets of the oldest networks.  A search object of its own (it replaces the self-play
+            # driver: what the ring had not yet handed to the window is dropped, as at the pit's re-creation below)
+            t0 = time.perf_counter()
+            eng.search_create(args.games, arena_nodes=1 << 13, seed=rnd, symmetry=args.symmetry, proof=args.proof)
+            reanalysed = eng.reanalyse(0, min(args.reanalyse_rows, eng.window_info()["count"]), args.reanalyse_rollouts or args.rollouts)
+            reanalysed["seconds"] = time.perf_counter() - t0
+            print(json.dumps({"round": rnd, "reanalyse": reanalysed}), flush=True)
         t0 = time.perf_counter()
         if args.window:
             # A fresh optimiser on the whole window (main.rs:82-95).  tg_window_train exchanges no verdicts between ranks: this loop
@@ -184,6 +206,7 @@ def main():
                 eng.load_state_dict(tensors)
                 eng.train_create(chunk_size=args.chunk, chunks_in_step=args.chunks_in_step)
             gate["accepted"] = gate["win_rate"] > 0.55
+        if old is not None or args.reanalyse_rows:  # the pit and the reanalysis both replaced the self-play driver
             eng.selfplay_create(args.games, arena_nodes=1 << 13, seed=rnd + 1, rollouts=args.rollouts, max_examples=4 * harvest,
                                 slot_base=tdist.slot_base(rank, args.games), **schedule)
         chunks = n_train // args.chunk if args.window else args.examples // args.chunk
@@ -194,6 +217,8 @@ def main():
             report[-1]["holdout"] = held_out
         if args.window:
             report[-1]["window"] = eng.window_info()
+        if reanalysed is not None:
+            report[-1]["reanalyse"] = reanalysed
         print(json.dumps(report[-1]), flush=True)
     eng.close()
     if old is not None:

@@ -124,6 +124,8 @@ int train_window(TgEngine* e, const WindowDev& W, uint32_t row0, int count, uint
                  int32_t* steps);
 // window.hip
 void window_destroy(Window* w);
+// the device arrays of the engine's window and its host-side counters (reanalyse.hip); false: the engine has no window
+bool window_view(const TgEngine* e, WindowDev* d, uint64_t* count, uint64_t* evicted);
 // solve.hip
 void solver_destroy(Solver* s);
 // symm.hip

@@ -278,4 +278,13 @@ hipError_t launch_window_absorb(hipStream_t st, const SelfPlayDev& P, const Wind
 hipError_t launch_window_gather(hipStream_t st, const WindowDev& W, uint32_t row0, const int32_t* order, int n, uint8_t* states,
                                 int32_t* n_moves, uint16_t* moves, uint32_t* visits, float* zt);
 
+// reanalyse_kernels.hip: window rows ↔ the roots of a search object (tg_reanalyse, reanalyse.hip)
+enum : uint8_t { REANALYSE_UPDATED = 1, REANALYSE_MISMATCHED = 2, REANALYSE_UNVISITED = 3 };  // a row's status byte; 0 = not reached
+// slot g < S.G: root_state[g] ← window row (row0 + g) % capacity and alive for g < k, dead for the others; op[g] = −2 (the reset
+// of launch_reroot) for all of them.  row0 < capacity, k ≤ min(S.G, capacity), W.bytes = the search's state size
+hipError_t launch_reanalyse_roots(hipStream_t st, const SearchDev& S, const WindowDev& W, uint32_t row0, int k, int32_t* op);
+// slot g < k: the root's children's visits → the visits of window row (row0 + g) % capacity where the children are the row's move
+// list and have a visit; status[g] = REANALYSE_* either way
+hipError_t launch_reanalyse_store(hipStream_t st, const SearchDev& S, const WindowDev& W, uint32_t row0, int k, uint8_t* status);
+
 }  // namespace tg

@@ -57,7 +57,7 @@ static int upload_mask(TgEngine* e, const uint8_t* active, const uint8_t** d_out
 
 // Every chunk but chunk 0 free, no game owning one: the state after create and after tg_search_reset (which drops every
 // tree, and with them a pool that an exhaustion has left inconsistent).  search_reset_trees then gives each game its root chunk.
-static int pool_init(TgEngine* e, Search* s) {
+int pool_init(TgEngine* e, Search* s) {
     const size_t G = (size_t)s->cfg.games, n_chunks = s->d.n_chunks;
     const int chunk_shift = s->d.chunk_shift;
     std::vector<uint32_t> ring(n_chunks, 0u);

@@ -43,6 +43,7 @@ struct Search {
     int proof = 0;  // tg_search_set_proof: TG_PROOF_ON = the selects and the self-play pick of search_proof_kernels.hip
     bool proof_ran = false;  // iterations have run under TG_PROOF_ON since the trees were last reset: they may hold TG_PROVEN_* codes
     DevBuf p_root, p_child, p_counts;  // tg_search_proof
+    DevBuf re_status;                  // tg_reanalyse: one status byte per row of the call's range
     // rollout schedule (tg_selfplay_set_schedule): games under boost_plies run boost_factor × rollouts iterations, the extra
     // ones over a compacted list of those games
     TgRolloutSchedule sched{};
@@ -60,6 +61,7 @@ int read_counters(TgEngine* e, unsigned long long* expansions, unsigned long lon
 // driver runs `rollouts` ITERATIONS per move whatever the batch, so its trees are `batch` times larger; a caller-driven search
 // decides its own iteration count (1).  Only the automatic pool size looks at it.
 int search_alloc(TgEngine* e, const TgSearchConfig* cfg, size_t tree_growth = 1);
+int pool_init(TgEngine* e, Search* s);  // every chunk but chunk 0 free, no game owning one (tg_search_reset, tg_reanalyse); synchronises
 int search_reset_trees(TgEngine* e);  // every tree = Node::default(), every game alive with the given root state
 // `iters` lock-step iterations, no host synchronisation inside: over the games of the device mask `d_active` (null: all), or over
 // the compacted `list` of `count` games (null: all)

@@ -24,6 +24,14 @@ struct Window {
 
 void window_destroy(Window* w) { delete w; }
 
+bool window_view(const TgEngine* e, WindowDev* d, uint64_t* count, uint64_t* evicted) {
+    if (!e || !e->window) return false;
+    *d = e->window->d;
+    *count = e->window->count();
+    *evicted = e->window->evicted();
+    return true;
+}
+
 namespace {
 
 int need_window(TgEngine* e, const char* who) {

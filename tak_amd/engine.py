@@ -69,6 +69,18 @@ class TgWindowInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class TgReanalyseConfig(C.Structure):
+    _fields_ = [("rollouts", C.c_int32), ("noise_alpha", C.c_float), ("noise_ratio", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class TgReanalyseStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("rows", "updated", "mismatched", "unvisited", "expansions", "evals")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class TgSelfPlayStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in (
         "games_finished", "examples", "expansions", "evals", "plies", "white_wins", "black_wins", "draws", "instant_wins",
@@ -152,6 +164,7 @@ ABI_SYMBOLS = [
     "tg_selfplay_create", "tg_selfplay_step", "tg_selfplay_stats", "tg_selfplay_drain",
     "tg_selfplay_set_schedule", "tg_selfplay_schedule_stats",
     "tg_window_create", "tg_window_info", "tg_window_clear", "tg_window_absorb", "tg_window_push", "tg_window_read", "tg_window_train",
+    "tg_reanalyse",
     "tg_profile_enable", "tg_profile_read", "tg_board_pass_bench",
     "tg_augment_examples", "tg_eval_examples",
     "tg_train_create", "tg_train_chunk", "tg_train", "tg_train_step", "tg_train_forward", "tg_train_get_tensor",
@@ -977,3 +990,12 @@ class Engine:
         lp, lz, steps = C.c_float(0), C.c_float(0), C.c_int32(0)
         self._check(self.lib.tg_window_train(self.h, int(first), int(count), C.c_uint64(seed), C.byref(lp), C.byref(lz), C.byref(steps)))
         return lp.value, lz.value, steps.value
+
+    def reanalyse(self, first, count, rollouts, noise_alpha=0.0, noise_ratio=0.0):
+        """tg_reanalyse: search the positions of logical window rows [first, first + count) again on the live search object
+        (search_create: its games, batch, seed, symmetry and proof modes; its trees are destroyed) and write the new root visit
+        counts into the rows in place, on the device -> {rows, updated, mismatched, unvisited, expansions, evals}"""
+        cfg = TgReanalyseConfig(int(rollouts), float(noise_alpha), float(noise_ratio), 0)
+        stats = TgReanalyseStats()
+        self._check(self.lib.tg_reanalyse(self.h, int(first), int(count), C.byref(cfg), C.byref(stats)))
+        return stats.as_dict()
