@@ -1,123 +1,29 @@
-"""ctypes binding of libtakgpu.so (C ABI: include/takgpu.h)."""
+"""ctypes binding of libtakgpu.so (C ABI: include/takgpu.h).  The structures, constants and function signatures come from the
+header itself (abi.py); what is written here is the Python surface: Engine, the text formats, pit."""
 import ctypes as C
 import os
 import subprocess
 
 import numpy as np
 
+from . import abi
+from .abi import *  # noqa: F401,F403  every Tg* structure and TG_* constant of include/takgpu.h, and ALLREDUCE_FN
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TAKGPU_LIB") or os.path.join(_HERE, "libtakgpu.so")  # TAKGPU_LIB: probe builds (scripts/probes)
-
-TG_ABI_VERSION = 5
-TG_MAX_MOVES = 512
-TG_DEBUG_MAX_DEPTH = 64
-TG_SOLVE_MAX_DEPTH = 6
-TG_SOLVE_ALL_MOVES = 1
-HEAD_FC5, HEAD_CONV = 0, 1
-EVAL_RESNET, EVAL_DUMMY, EVAL_HASH = 0, 1, 2
-
-NODE_RECORD = np.dtype(
-    [("move", "<u2"), ("n_children", "<u2"), ("visits", "<u4"), ("virtual_visits", "<u4"), ("result", "<u4"),
-     ("prior_bits", "<u4"), ("q_bits", "<u4")]
-)
-EXAMPLE_HEADER = np.dtype([("game_id", "<i4"), ("n_moves", "<i4"), ("result", "<f4"), ("reserved", "<i4")])
+ABI_SYMBOLS = list(abi.FUNCTIONS)  # every symbol include/takgpu.h declares (tests check the library exports all of them)
+HEAD_FC5, HEAD_CONV = TG_HEAD_FC5, TG_HEAD_CONV
+EVAL_RESNET, EVAL_DUMMY, EVAL_HASH = TG_EVAL_RESNET, TG_EVAL_DUMMY, TG_EVAL_HASH
+SYMM_OFF, SYMM_HASHED = TG_SYMM_OFF, TG_SYMM_HASHED
+PROOF_OFF, PROOF_ON = TG_PROOF_OFF, TG_PROOF_ON
+PROVEN_WHITE, PROVEN_BLACK, PROVEN_DRAW = TG_PROVEN_WHITE, TG_PROVEN_BLACK, TG_PROVEN_DRAW  # node-record codes beside the TgResult ones
+NODE_RECORD, EXAMPLE_HEADER = np.dtype(TgNodeRecord), np.dtype(TgExampleHeader)
 
 
 class TgError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"takgpu error {code}: {msg}")
         self.code = code
-
-
-class TgConfig(C.Structure):
-    _fields_ = [(k, C.c_int32) for k in (
-        "abi_version", "device", "board_size", "res_blocks", "filters", "policy_head", "evaluator", "max_batch")]
-
-
-class TgSearchConfig(C.Structure):
-    _fields_ = [("games", C.c_int32), ("arena_nodes", C.c_int32), ("exploration_base", C.c_float),
-                ("exploration_init", C.c_float), ("seed", C.c_uint64), ("slot_base", C.c_uint32), ("batch", C.c_uint32),
-                ("visit_limit", C.c_int32), ("reserved", C.c_int32)]
-
-
-class TgSolveConfig(C.Structure):
-    _fields_ = [("depth", C.c_int32), ("flags", C.c_uint32), ("node_budget", C.c_uint64), ("reserved", C.c_int32 * 4)]
-
-
-class TgProfile(C.Structure):
-    _fields_ = [("conv_launches", C.c_uint64), ("conv_ms", C.c_double), ("forwards", C.c_uint64), ("forward_ms", C.c_double),
-                ("conv_rows", C.c_int64), ("conv_flops", C.c_int64), ("conv_flops_executed", C.c_int64)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
-class TgSelfPlayConfig(C.Structure):
-    _fields_ = [("rollouts", C.c_int32), ("noise_plies", C.c_int32), ("exploit_plies", C.c_int32),
-                ("noise_alpha", C.c_float), ("noise_ratio", C.c_float), ("komi", C.c_int32),
-                ("total_games", C.c_int32), ("max_examples", C.c_int32), ("max_game_plies", C.c_int32), ("batch", C.c_int32)]
-
-
-class TgRolloutSchedule(C.Structure):
-    _fields_ = [("boost_plies", C.c_int32), ("boost_factor", C.c_int32), ("reserved", C.c_int32 * 2)]
-
-
-class TgWindowInfo(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("capacity", "count", "entered", "evicted")]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
-
-
-class TgReanalyseConfig(C.Structure):
-    _fields_ = [("rollouts", C.c_int32), ("noise_alpha", C.c_float), ("noise_ratio", C.c_float), ("flags", C.c_uint32),
-                ("reserved", C.c_int32 * 4)]
-
-
-class TgReanalyseStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("rows", "updated", "mismatched", "unvisited", "expansions", "evals")]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
-
-
-class TgSelfPlayStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in (
-        "games_finished", "examples", "expansions", "evals", "plies", "white_wins", "black_wins", "draws", "instant_wins",
-        "dropped_examples", "aborted_games", "alive_games")]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
-
-
-class TgTrainConfig(C.Structure):
-    _fields_ = [("learning_rate", C.c_float), ("weight_decay", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
-                ("eps", C.c_float), ("bn_momentum", C.c_float), ("bn_eps", C.c_float), ("chunk_size", C.c_int32),
-                ("chunks_in_step", C.c_int32), ("reserved", C.c_int32)]
-
-
-class TgPitConfig(C.Structure):
-    _fields_ = [("pairs", C.c_int32), ("rollouts", C.c_int32), ("idle_rollouts", C.c_int32), ("random_plies", C.c_int32),
-                ("komi", C.c_int32), ("max_plies", C.c_int32), ("arena_nodes", C.c_int32), ("batch", C.c_int32),
-                ("seed", C.c_uint64)]
-
-
-class TgPitResult(C.Structure):
-    _fields_ = [("wins", C.c_uint32), ("losses", C.c_uint32), ("draws", C.c_uint32), ("unfinished", C.c_uint32),
-                ("plies", C.c_uint32), ("reserved", C.c_uint32), ("win_rate", C.c_double),
-                ("ref_wins", C.c_uint32), ("ref_losses", C.c_uint32), ("ref_draws", C.c_uint32), ("ref_pairs", C.c_uint32),
-                ("ref_win_rate", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
-
-
-class TgExampleMetrics(C.Structure):
-    _fields_ = [("loss_p", C.c_double), ("loss_z", C.c_double), ("target_entropy", C.c_double), ("top1", C.c_uint64),
-                ("sign_ok", C.c_uint64), ("decided", C.c_uint64), ("positions", C.c_uint64)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 def example_means(sums):
@@ -130,53 +36,6 @@ def example_means(sums):
             "value_sign": sums["sign_ok"] / sums["decided"] if sums["decided"] else nan}
 
 
-class TgCommInfo(C.Structure):
-    _fields_ = [("attached", C.c_int32), ("world_size", C.c_int32), ("rank", C.c_int32), ("nccl_count", C.c_int32),
-                ("nccl_rank", C.c_int32), ("nccl_version", C.c_int32), ("lib_was_mapped", C.c_int32), ("reserved", C.c_int32),
-                ("lib_path", C.c_char * 256)]
-
-    def as_dict(self):
-        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in ("reserved", "lib_path")}
-        d["lib_path"] = self.lib_path.decode(errors="replace")
-        return d
-
-
-class TgDeviceInfo(C.Structure):
-    _fields_ = [("hip_device", C.c_int32), ("cu_count", C.c_int32), ("clock_khz", C.c_int32), ("reserved", C.c_int32),
-                ("total_mem", C.c_uint64), ("pci_bus_id", C.c_char * 32), ("name", C.c_char * 128), ("arch", C.c_char * 64)]
-
-    def as_dict(self):
-        return {"hip_device": int(self.hip_device), "pci_bus_id": self.pci_bus_id.decode(errors="replace"),
-                "name": self.name.decode(errors="replace"), "arch": self.arch.decode(errors="replace"),
-                "cu_count": int(self.cu_count), "clock_khz": int(self.clock_khz), "total_mem": int(self.total_mem)}
-
-
-# every symbol include/takgpu.h declares (tests check the library exports all of them)
-ABI_SYMBOLS = [
-    "tg_state_bytes", "tg_engine_create", "tg_engine_destroy", "tg_last_error", "tg_sync", "tg_stream", "tg_device_info", "tg_debug_switches",
-    "tg_input_channels", "tg_policy_size", "tg_movegen", "tg_play", "tg_result", "tg_encode", "tg_move_index",
-    "tg_perft", "tg_net_set_tensor", "tg_net_init_random", "tg_net_get_tensor", "tg_net_finalize", "tg_net_set_precision", "tg_policy_eval", "tg_forward_mcts", "tg_policy_eval_dev",
-    "tg_policy_eval_symm", "tg_policy_eval_symm_dev", "tg_symm_perm_read", "tg_search_set_symmetry", "tg_search_get_symmetry",
-    "tg_search_create", "tg_search_reset", "tg_search_run", "tg_search_apply_dirichlet", "tg_search_apply_noise",
-    "tg_search_root", "tg_search_play", "tg_search_states", "tg_search_dump", "tg_search_debug", "tg_search_counters", "tg_search_pool",
-    "tg_search_set_proof", "tg_search_get_proof", "tg_search_proof",
-    "tg_solve", "tg_search_solve",
-    "tg_selfplay_create", "tg_selfplay_step", "tg_selfplay_stats", "tg_selfplay_drain",
-    "tg_selfplay_set_schedule", "tg_selfplay_schedule_stats",
-    "tg_window_create", "tg_window_info", "tg_window_clear", "tg_window_absorb", "tg_window_push", "tg_window_read", "tg_window_train",
-    "tg_reanalyse",
-    "tg_profile_enable", "tg_profile_read", "tg_board_pass_bench",
-    "tg_augment_examples", "tg_eval_examples",
-    "tg_train_create", "tg_train_chunk", "tg_train", "tg_train_step", "tg_train_forward", "tg_train_get_tensor",
-    "tg_train_get_grad", "tg_train_debug_capture", "tg_train_debug_read", "tg_train_commit", "tg_comm_unique_id", "tg_train_comm_init", "tg_train_set_allreduce",
-    "tg_train_grad_buffer", "tg_train_comm_stats", "tg_train_comm_info", "tg_train_comm_preflight", "tg_train_order", "tg_pit",
-    "tg_format_move", "tg_parse_move", "tg_format_tps", "tg_parse_tps", "tg_format_example", "tg_parse_example",
-]
-
-
-SYMM_OFF, SYMM_HASHED = 0, 1  # TgSearchSymmetry
-
-
 def _symmetry_mode(mode):
     if isinstance(mode, str):
         if mode not in ("off", "hashed"):
@@ -185,8 +44,6 @@ def _symmetry_mode(mode):
     return int(mode)
 
 
-PROOF_OFF, PROOF_ON = 0, 1  # TgSearchProof
-PROVEN_WHITE, PROVEN_BLACK, PROVEN_DRAW = 8, 9, 10  # TgProven: node-record codes beside the TgResult ones
 STATUS_WHITE, STATUS_BLACK, STATUS_DRAW, STATUS_UNKNOWN = 0, 1, 2, 3
 _STATUS_OF_CODE = np.array([3, 0, 0, 1, 1, 2, 2, 3, 0, 1, 2, 3, 3, 3, 3, 3], np.uint8)
 
@@ -203,9 +60,6 @@ def _proof_mode(mode):
             raise ValueError(f"proof must be 'off' or 'on', not {mode!r}")
         return PROOF_ON if mode == "on" else PROOF_OFF
     return int(mode)  # (True / False too)
-
-
-ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
 def device_to_host(d_ptr, count, stream=None):
@@ -241,17 +95,7 @@ def load_library():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise FileNotFoundError(f"{LIB_PATH} is missing: build it with tak_amd.build_library() / __graft_entry__.build()")
-        l = C.CDLL(LIB_PATH)
-        l.tg_state_bytes.restype = C.c_size_t
-        l.tg_last_error.restype = C.c_char_p
-        l.tg_stream.restype = C.c_void_p
-        l.tg_stream.argtypes = [C.c_void_p]
-        l.tg_engine_create.argtypes = [C.c_void_p, C.c_void_p]
-        l.tg_engine_destroy.argtypes = [C.c_void_p]
-        l.tg_engine_destroy.restype = None
-        for name in ABI_SYMBOLS:
-            getattr(l, name)
-        _lib = l
+        _lib = abi.declare(C.CDLL(LIB_PATH))  # the header's restype and argtypes on every entry point; a missing export raises
     return _lib
 
 
@@ -271,8 +115,10 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
-def _text_check(rc):
-    if rc < 0:
+def _check(rc, length=False):
+    """anything but TG_OK → TgError with tg_last_error's message; length=True: the tg_format_* functions, which return a text
+    length ≥ 0 or a negative TgStatus"""
+    if rc < 0 or (rc and not length):
         raise TgError(rc, load_library().tg_last_error().decode())
     return rc
 
@@ -280,26 +126,26 @@ def _text_check(rc):
 # ---- text formats (host only; no GPU needed): PTN, TPS, example lines of alpha-tak/src/example.rs:81-133 ----
 def format_move(n, code):
     buf = C.create_string_buffer(32)
-    _text_check(load_library().tg_format_move(n, C.c_uint16(int(code)), buf, C.c_size_t(32)))
+    _check(load_library().tg_format_move(n, int(code), buf, 32), length=True)
     return buf.value.decode()
 
 
 def parse_move(n, text):
     out = C.c_uint16(0)
-    _text_check(load_library().tg_parse_move(n, text.encode(), C.byref(out)))
+    _check(load_library().tg_parse_move(n, text.encode(), C.byref(out)))
     return out.value
 
 
 def format_tps(n, state):
     st = np.ascontiguousarray(state, np.uint8)
     buf = C.create_string_buffer(2048)
-    _text_check(load_library().tg_format_tps(n, _p(st), buf, C.c_size_t(2048)))
+    _check(load_library().tg_format_tps(n, _p(st), buf, 2048), length=True)
     return buf.value.decode()
 
 
 def parse_tps(n, text):
     st = np.zeros(state_bytes(n), np.uint8)
-    _text_check(load_library().tg_parse_tps(n, text.encode(), _p(st)))
+    _check(load_library().tg_parse_tps(n, text.encode(), _p(st)))
     return st
 
 
@@ -308,7 +154,7 @@ def format_example(n, state, moves, visits, result):
     mv = np.ascontiguousarray(moves, np.uint16)
     vs = np.ascontiguousarray(visits, np.uint32)
     buf = C.create_string_buffer(1 << 14)
-    _text_check(load_library().tg_format_example(n, _p(st), int(mv.size), _p(mv), _p(vs), C.c_float(float(result)), buf, C.c_size_t(1 << 14)))
+    _check(load_library().tg_format_example(n, _p(st), mv.size, _p(mv), _p(vs), float(result), buf, 1 << 14), length=True)
     return buf.value.decode()
 
 
@@ -318,7 +164,7 @@ def parse_example(n, line):
     vs = np.zeros(TG_MAX_MOVES, np.uint32)
     k = C.c_int32(0)
     res = C.c_float(0)
-    _text_check(load_library().tg_parse_example(n, line.encode(), _p(st), TG_MAX_MOVES, _p(mv), _p(vs), C.byref(k), C.byref(res)))
+    _check(load_library().tg_parse_example(n, line.encode(), _p(st), TG_MAX_MOVES, _p(mv), _p(vs), C.byref(k), C.byref(res)))
     return st, mv[: k.value].copy(), vs[: k.value].copy(), res.value
 
 
@@ -348,9 +194,7 @@ def read_examples(n, paths):
 def comm_unique_id():
     """ncclGetUniqueId on this rank (128 bytes); broadcast it to the other ranks with any host transport."""
     uid = np.zeros(128, np.uint8)
-    rc = load_library().tg_comm_unique_id(_p(uid))
-    if rc:
-        raise TgError(rc, load_library().tg_last_error().decode())
+    _check(load_library().tg_comm_unique_id(_p(uid)))
     return uid.tobytes()
 
 
@@ -358,7 +202,7 @@ def debug_switches():
     """the TG_* A/B switches that are ON in this process's environment, as the library reads them → ["NAME=value", …];
     [] on a measured run (tg_debug_switches; needs no GPU)"""
     buf = C.create_string_buffer(4096)
-    n = load_library().tg_debug_switches(buf, C.c_size_t(4096))
+    n = load_library().tg_debug_switches(buf, 4096)
     out = buf.value.decode().split()
     assert n == len(out), (n, out)
     return out
@@ -367,7 +211,7 @@ def debug_switches():
 def train_order(seed, n):
     """the permutation tg_train(seed) visits n examples in (tg_train_order)"""
     order = np.zeros(n, np.int32)
-    _text_check(load_library().tg_train_order(C.c_uint64(seed), n, _p(order)))
+    _check(load_library().tg_train_order(seed, n, _p(order)))
     return order
 
 
@@ -382,9 +226,7 @@ def pit(new, old, pairs=128, rollouts=50, batch=16, idle_rollouts=1, random_plie
         old.search_set_symmetry(symmetry)
     cfg = TgPitConfig(pairs, rollouts, idle_rollouts, random_plies, komi, max_plies, arena_nodes, batch, seed)
     res = TgPitResult()
-    rc = load_library().tg_pit(new.h, old.h, C.byref(cfg), C.byref(res))
-    if rc:
-        raise TgError(rc, load_library().tg_last_error().decode())
+    _check(load_library().tg_pit(new.h, old.h, C.byref(cfg), C.byref(res)))
     return res.as_dict()
 
 
@@ -455,9 +297,7 @@ class Engine:
         except Exception:
             pass
 
-    def _check(self, rc):
-        if rc != 0:
-            raise TgError(rc, self.lib.tg_last_error().decode())
+    _check = staticmethod(_check)
 
     def _states(self, states):
         states = np.ascontiguousarray(states, np.uint8).reshape(-1, self.sb)
@@ -544,7 +384,7 @@ class Engine:
         """Network::train over a set of examples → (mean loss_p, mean loss_z, optimiser steps)"""
         states, k, n_moves, moves, visits, results = self._examples(states, n_moves, moves, visits, results)
         lp, lz, steps = C.c_float(0), C.c_float(0), C.c_int32(0)
-        self._check(self.lib.tg_train(self.h, k, _p(states), _p(n_moves), _p(moves), _p(visits), _p(results), C.c_uint64(seed),
+        self._check(self.lib.tg_train(self.h, k, _p(states), _p(n_moves), _p(moves), _p(visits), _p(results), seed,
                                       C.byref(lp), C.byref(lz), C.byref(steps)))
         return lp.value, lz.value, steps.value
 
@@ -561,12 +401,12 @@ class Engine:
 
     def train_get_tensor(self, name, shape):
         out = np.zeros(shape, np.float32)
-        self._check(self.lib.tg_train_get_tensor(self.h, name.encode(), _p(out), C.c_size_t(out.size)))
+        self._check(self.lib.tg_train_get_tensor(self.h, name.encode(), _p(out), out.size))
         return out
 
     def train_get_grad(self, name, shape):
         out = np.zeros(shape, np.float32)
-        self._check(self.lib.tg_train_get_grad(self.h, name.encode(), _p(out), C.c_size_t(out.size)))
+        self._check(self.lib.tg_train_get_grad(self.h, name.encode(), _p(out), out.size))
         return out
 
     def train_debug_capture(self, layer):
@@ -576,7 +416,7 @@ class Engine:
     def train_debug_read(self, what, layer, shape):
         """an intermediate tensor of the last training chunk / forward (include/takgpu.h tg_train_debug_read)"""
         out = np.zeros(shape, np.float32)
-        self._check(self.lib.tg_train_debug_read(self.h, what.encode(), int(layer), _p(out), C.c_size_t(out.size)))
+        self._check(self.lib.tg_train_debug_read(self.h, what.encode(), int(layer), _p(out), out.size))
         return out
 
     def train_commit(self):
@@ -591,8 +431,7 @@ class Engine:
         sums = TgExampleMetrics()
         out = np.zeros((k * (8 if symmetries else 1), 4), np.float32) if rows else None
         self._check(self.lib.tg_eval_examples(self.h, k, _p(states), _p(n_moves), _p(moves), _p(visits), _p(results),
-                                              C.c_int(1 if symmetries is True else 0 if symmetries is False else int(symmetries)),
-                                              C.byref(sums), _p(out) if rows else None))
+                                              int(symmetries), C.byref(sums), _p(out) if rows else None))
         res = example_means(sums.as_dict())
         res["sums"] = sums.as_dict()
         if rows:
@@ -659,7 +498,7 @@ class Engine:
     # ---- Network<N> -------------------------------------------------------------------------------
     def set_tensor(self, name, array):
         a = np.ascontiguousarray(array, np.float32)
-        self._check(self.lib.tg_net_set_tensor(self.h, name.encode(), _p(a), C.c_size_t(a.size)))
+        self._check(self.lib.tg_net_set_tensor(self.h, name.encode(), _p(a), a.size))
 
     def set_precision(self, precision):
         """"f32" (exact, default) or "bf16x3" (split-bf16 tower); takes effect at the next load_state_dict / finalize"""
@@ -667,14 +506,14 @@ class Engine:
 
     def init_random(self, seed=0, finalize=True):
         """Network::default(): tch's default initialisers drawn from Philox(seed) (tg_net_init_random)."""
-        self._check(self.lib.tg_net_init_random(self.h, C.c_uint64(seed)))
+        self._check(self.lib.tg_net_init_random(self.h, seed))
         if finalize:
             self._check(self.lib.tg_net_finalize(self.h))
 
     def get_tensor(self, name, shape):
         """the tensor as last set / initialised / committed (tg_net_get_tensor) — what Network::save writes"""
         out = np.zeros(shape, np.float32)
-        self._check(self.lib.tg_net_get_tensor(self.h, name.encode(), _p(out), C.c_size_t(out.size)))
+        self._check(self.lib.tg_net_get_tensor(self.h, name.encode(), _p(out), out.size))
         return out
 
     def state_dict(self):
@@ -697,12 +536,11 @@ class Engine:
         if symmetries is None:
             self._check(self.lib.tg_policy_eval(self.h, k, _p(states), _p(policy), _p(ev)))
         else:
-            self._check(self.lib.tg_policy_eval_symm(self.h, k, _p(states), C.c_uint32(int(symmetries)), _p(policy), _p(ev)))
+            self._check(self.lib.tg_policy_eval_symm(self.h, k, _p(states), int(symmetries), _p(policy), _p(ev)))
         return policy, ev
 
     def policy_eval_symm_dev(self, n, d_states, mask, d_policy, d_eval):
-        self._check(self.lib.tg_policy_eval_symm_dev(self.h, n, C.c_void_p(d_states), C.c_uint32(int(mask)), C.c_void_p(d_policy),
-                                                     C.c_void_p(d_eval)))
+        self._check(self.lib.tg_policy_eval_symm_dev(self.h, n, d_states, int(mask), d_policy, d_eval))
 
     def symm_perm(self):
         """the device's policy permutation tables [8, P] (tg_symm_perm_read): perm[s, j] = slot of the image under s of slot j's move"""
@@ -747,7 +585,7 @@ class Engine:
         return policy, ev
 
     def policy_eval_dev(self, n, d_states, d_policy, d_eval):
-        self._check(self.lib.tg_policy_eval_dev(self.h, n, C.c_void_p(d_states), C.c_void_p(d_policy), C.c_void_p(d_eval)))
+        self._check(self.lib.tg_policy_eval_dev(self.h, n, d_states, d_policy, d_eval))
 
     # ---- Node / search ----------------------------------------------------------------------------
     def search_create(self, games, arena_nodes=1 << 16, base=500.0, init=4.0, seed=0, slot_base=0, batch=1, visit_limit=0, symmetry=None,
@@ -772,11 +610,11 @@ class Engine:
         self._check(self.lib.tg_search_run(self.h, iters, _p(_mask(active))))
 
     def search_apply_dirichlet(self, alpha, ratio, active=None):
-        self._check(self.lib.tg_search_apply_dirichlet(self.h, C.c_float(alpha), C.c_float(ratio), _p(_mask(active))))
+        self._check(self.lib.tg_search_apply_dirichlet(self.h, alpha, ratio, _p(_mask(active))))
 
     def search_apply_noise(self, noise, ratio, active=None):
         noise = np.ascontiguousarray(noise, np.float32).reshape(self.games, TG_MAX_MOVES)
-        self._check(self.lib.tg_search_apply_noise(self.h, _p(noise), C.c_float(ratio), _p(_mask(active))))
+        self._check(self.lib.tg_search_apply_noise(self.h, _p(noise), ratio, _p(_mask(active))))
 
     def search_root(self):
         g = self.games
@@ -802,7 +640,7 @@ class Engine:
     def search_dump(self, game, capacity=1 << 20):
         rec = np.zeros(capacity, NODE_RECORD)
         nrec = C.c_size_t(0)
-        self._check(self.lib.tg_search_dump(self.h, game, _p(rec), C.c_size_t(capacity), C.byref(nrec)))
+        self._check(self.lib.tg_search_dump(self.h, game, _p(rec), capacity, C.byref(nrec)))
         return rec[: nrec.value].copy()
 
     def search_debug(self, depth=10, top_k=TG_MAX_MOVES):
@@ -988,7 +826,7 @@ class Engine:
         """Network::train on logical [first, first + count) of the window: bit for bit train() on those examples, oldest first
         -> (mean loss_p, mean loss_z, optimiser steps)"""
         lp, lz, steps = C.c_float(0), C.c_float(0), C.c_int32(0)
-        self._check(self.lib.tg_window_train(self.h, int(first), int(count), C.c_uint64(seed), C.byref(lp), C.byref(lz), C.byref(steps)))
+        self._check(self.lib.tg_window_train(self.h, int(first), int(count), seed, C.byref(lp), C.byref(lz), C.byref(steps)))
         return lp.value, lz.value, steps.value
 
     def reanalyse(self, first, count, rollouts, noise_alpha=0.0, noise_ratio=0.0):

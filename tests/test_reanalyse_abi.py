@@ -6,9 +6,10 @@ import inspect
 import os
 import re
 import subprocess
-import sys
 
 import pytest
+
+from abi_helpers import defined_symbols, parsed_header as _parsed_header, rust_fields, script as _script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "takgpu.h")
@@ -17,18 +18,6 @@ CONFIG = [("rollouts", "int32_t", None), ("noise_alpha", "float", None), ("noise
           ("reserved", "int32_t", 4)]
 STATS = [(f, "uint64_t", None) for f in ("rows", "updated", "mismatched", "unvisited", "expansions", "evals")]
 WINDOW_SEVEN = ["tg_window_absorb", "tg_window_clear", "tg_window_create", "tg_window_info", "tg_window_push", "tg_window_read", "tg_window_train"]
-
-
-def _script(name):
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    try:
-        return __import__(name)
-    finally:
-        sys.path.pop(0)
-
-
-def _parsed_header():
-    return _script("gen_rust_sys").parse_header(HEADER)
 
 
 def test_the_entry_point_is_declared_listed_and_exported_beside_the_windows_seven():
@@ -41,10 +30,7 @@ def test_the_entry_point_is_declared_listed_and_exported_beside_the_windows_seve
     script = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "tak_amd", "csrc", "exports.map")).read(), flags=re.S)
     patterns = re.search(r"global:(.*?)local:", script, flags=re.S).group(1).replace(";", " ").split()
     assert any(fnmatch.fnmatchcase("tg_reanalyse", p) for p in patterns), patterns
-    if not os.path.exists(tak_amd.LIB_PATH):
-        tak_amd.build_library()
-    out = subprocess.run(["nm", "-D", "--defined-only", tak_amd.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    defined = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    defined = defined_symbols()
     assert "tg_reanalyse" in defined
     assert sorted(n for n in defined if n.startswith("tg_window_")) == WINDOW_SEVEN
     assert "tg_reanalyse" in tak_amd.engine.ABI_SYMBOLS
@@ -84,11 +70,6 @@ def test_the_structures_have_the_same_layout_everywhere_and_the_abi_keeps_its_ve
     assert C.sizeof(cfg) == 32 and C.sizeof(stats) == 48 and engine.TG_ABI_VERSION == 5
     assert [getattr(cfg, f).offset for f, _, _ in CONFIG] == [0, 4, 8, 12, 16]
     rust = open(os.path.join(ROOT, "rust", "takgpu-sys", "src", "lib.rs")).read()
-
-    def rust_fields(name):
-        body = re.search(r"#\[repr\(C\)\]\s*#\[derive\([^)]*\)\]\s*pub struct " + name + r" \{(.*?)\}", rust, flags=re.S).group(1)
-        return [ln.strip().rstrip(",") for ln in body.strip().splitlines()]
-
     assert rust_fields("TgReanalyseConfig") == ["pub rollouts: i32", "pub noise_alpha: f32", "pub noise_ratio: f32", "pub flags: u32", "pub reserved: [i32; 4]"]
     assert rust_fields("TgReanalyseStats") == [f"pub {f}: u64" for f, _, _ in STATS]
     assert ("pub fn tg_reanalyse(e: *mut TgEngine, first: c_int, count: c_int, cfg: *const TgReanalyseConfig, out: *mut TgReanalyseStats) "

@@ -5,23 +5,15 @@ import fnmatch
 import os
 import re
 import subprocess
-import sys
 
 import pytest
+
+from abi_helpers import defined_symbols, parsed_header as _parsed_header, rust_fields, script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "takgpu.h")
 ENTRY_POINTS = ("tg_selfplay_set_schedule", "tg_selfplay_schedule_stats")
 FIELDS = [("boost_plies", "int32_t", None), ("boost_factor", "int32_t", None), ("reserved", "int32_t", 2)]
-
-
-def _parsed_header():
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    try:
-        import gen_rust_sys
-    finally:
-        sys.path.pop(0)
-    return gen_rust_sys.parse_header(HEADER)
 
 
 def test_both_entry_points_are_declared_listed_and_exported():
@@ -34,10 +26,7 @@ def test_both_entry_points_are_declared_listed_and_exported():
     # the version script exports by pattern: the globals' patterns cover both names, and no local pattern comes first
     script = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "tak_amd", "csrc", "exports.map")).read(), flags=re.S)
     patterns = re.search(r"global:(.*?)local:", script, flags=re.S).group(1).replace(";", " ").split()
-    if not os.path.exists(tak_amd.LIB_PATH):
-        tak_amd.build_library()
-    out = subprocess.run(["nm", "-D", "--defined-only", tak_amd.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    defined = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    defined = defined_symbols()
     for name in ENTRY_POINTS:
         assert any(fnmatch.fnmatchcase(name, p) for p in patterns), (name, patterns)
         assert name in defined, name
@@ -79,8 +68,7 @@ def test_the_structure_is_the_same_16_bytes_in_header_ctypes_and_rust(tmp_path):
     assert C.sizeof(engine.TgSelfPlayConfig) == 40 and engine.TG_ABI_VERSION == 5
     # Rust: the raw binding's struct and functions, and the safe wrapper's settings
     rust = open(os.path.join(ROOT, "rust", "takgpu-sys", "src", "lib.rs")).read()
-    body = re.search(r"#\[repr\(C\)\]\s*#\[derive\([^)]*\)\]\s*pub struct TgRolloutSchedule \{(.*?)\}", rust, flags=re.S).group(1)
-    assert [ln.strip().rstrip(",") for ln in body.strip().splitlines()] == ["pub boost_plies: i32", "pub boost_factor: i32", "pub reserved: [i32; 2]"]
+    assert rust_fields("TgRolloutSchedule") == ["pub boost_plies: i32", "pub boost_factor: i32", "pub reserved: [i32; 2]"]
     assert "pub fn tg_selfplay_set_schedule(e: *mut TgEngine, s: *const TgRolloutSchedule) -> c_int;" in rust
     assert ("pub fn tg_selfplay_schedule_stats(e: *mut TgEngine, boosted_moves: *mut u64, compact_iterations: *mut u64, "
             "compact_leaves: *mut u64) -> c_int;") in rust
@@ -103,11 +91,7 @@ def test_the_python_keywords_default_to_off():
 
 
 def _train_loop():
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    try:
-        import train_loop
-    finally:
-        sys.path.pop(0)
+    train_loop = script("train_loop")
     return train_loop
 
 

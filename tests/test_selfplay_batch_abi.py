@@ -4,20 +4,17 @@ import ctypes as C
 import os
 import re
 import subprocess
-import sys
+
+from abi_helpers import parsed_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "takgpu.h")
+
 CTYPES = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "float": C.c_float, "uint64_t": C.c_uint64}
 
 
 def _header_fields(struct):
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    try:
-        import gen_rust_sys
-    finally:
-        sys.path.pop(0)
-    structs = dict(gen_rust_sys.parse_header(HEADER)["structs"])
+    structs = dict(parsed_header()["structs"])
     return [(name, ctype) for name, ctype, array in structs[struct]]
 
 

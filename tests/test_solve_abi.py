@@ -4,20 +4,14 @@ import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 
+from abi_helpers import defined_symbols, parsed_header as _header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 NEW = ("tg_solve", "tg_search_solve")
-
-
-def _header():
-    import gen_rust_sys
-
-    return gen_rust_sys.parse_header()
 
 
 def test_the_two_exports_are_in_header_rust_binding_python_table_and_library():
@@ -34,8 +28,7 @@ def test_the_two_exports_are_in_header_rust_binding_python_table_and_library():
     assert [a for _, a in fns["tg_solve"]] == ["e", "n", "states", "cfg", "value", "best", "counts", "moves", "move_values", "budget_hit", "nodes"]
     assert [a for _, a in fns["tg_search_solve"]] == ["e", "cfg", "active", "value", "best", "counts", "moves", "move_values", "budget_hit", "nodes"]
     assert [t for t, _ in fns["tg_solve"]][4:] == ["int8_t*", "TgMove*", "int32_t*", "TgMove*", "int8_t*", "uint8_t*", "uint64_t*"]
-    out = subprocess.run(["nm", "-D", "--defined-only", tak_amd.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    defined = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    defined = defined_symbols()
     assert defined == {name for name, _, _ in h["functions"]}  # `nm -D` is still the header, no more and no less
     assert dict(h["defines"])["TG_ABI_VERSION"] == 5 and dict(h["defines"])["TG_SOLVE_MAX_DEPTH"] == 6
 

@@ -6,9 +6,10 @@ import inspect
 import os
 import re
 import subprocess
-import sys
 
 import pytest
+
+from abi_helpers import defined_symbols, parsed_header as _parsed_header, script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "takgpu.h")
@@ -23,15 +24,6 @@ DECLARATIONS = {
 }
 
 
-def _parsed_header():
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    try:
-        import gen_rust_sys
-    finally:
-        sys.path.pop(0)
-    return gen_rust_sys.parse_header(HEADER)
-
-
 def test_the_entry_points_are_declared_listed_and_exported():
     import tak_amd
 
@@ -40,10 +32,7 @@ def test_the_entry_points_are_declared_listed_and_exported():
         assert functions[name] == ("int", args), name
     script = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "tak_amd", "csrc", "exports.map")).read(), flags=re.S)
     patterns = re.search(r"global:(.*?)local:", script, flags=re.S).group(1).replace(";", " ").split()
-    if not os.path.exists(tak_amd.LIB_PATH):
-        tak_amd.build_library()
-    out = subprocess.run(["nm", "-D", "--defined-only", tak_amd.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    defined = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    defined = defined_symbols()
     for name in DECLARATIONS:
         assert any(fnmatch.fnmatchcase(name, p) for p in patterns), (name, patterns)
         assert name in defined, name
@@ -138,11 +127,7 @@ def test_argument_errors_that_need_no_device():
 
 
 def test_the_loop_script_takes_the_symmetry_and_defaults_to_off():
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    try:
-        import train_loop
-    finally:
-        sys.path.pop(0)
+    train_loop = script("train_loop")
     assert train_loop.parse_args([]).symmetry == "off"
     assert train_loop.parse_args(["--symmetry", "hashed"]).symmetry == "hashed"
     with pytest.raises(SystemExit) as ei:

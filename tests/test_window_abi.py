@@ -6,9 +6,10 @@ import inspect
 import os
 import re
 import subprocess
-import sys
 
 import pytest
+
+from abi_helpers import defined_symbols, parsed_header as _parsed_header, rust_fields, script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "takgpu.h")
@@ -27,15 +28,6 @@ DECLARATIONS = {
 WRAPPERS = ("window_create", "window_info", "window_clear", "window_absorb", "window_push", "window_read", "window_train")
 
 
-def _parsed_header():
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    try:
-        import gen_rust_sys
-    finally:
-        sys.path.pop(0)
-    return gen_rust_sys.parse_header(HEADER)
-
-
 def test_the_seven_entry_points_are_declared_listed_and_exported():
     import tak_amd
 
@@ -45,10 +37,7 @@ def test_the_seven_entry_points_are_declared_listed_and_exported():
     assert sorted(n for n in functions if n.startswith("tg_window_")) == sorted(DECLARATIONS)
     script = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "tak_amd", "csrc", "exports.map")).read(), flags=re.S)
     patterns = re.search(r"global:(.*?)local:", script, flags=re.S).group(1).replace(";", " ").split()
-    if not os.path.exists(tak_amd.LIB_PATH):
-        tak_amd.build_library()
-    out = subprocess.run(["nm", "-D", "--defined-only", tak_amd.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    defined = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    defined = defined_symbols()
     for name in DECLARATIONS:
         assert any(fnmatch.fnmatchcase(name, p) for p in patterns), (name, patterns)
         assert name in defined, name
@@ -89,8 +78,7 @@ def test_the_structure_is_the_same_32_bytes_everywhere_and_the_abi_keeps_its_ver
     assert [(f, t) for f, t in S._fields_] == [(f, C.c_uint64) for f in ("capacity", "count", "entered", "evicted")]
     assert C.sizeof(S) == 32 and engine.TG_ABI_VERSION == 5
     rust = open(os.path.join(ROOT, "rust", "takgpu-sys", "src", "lib.rs")).read()
-    body = re.search(r"#\[repr\(C\)\]\s*#\[derive\([^)]*\)\]\s*pub struct TgWindowInfo \{(.*?)\}", rust, flags=re.S).group(1)
-    assert [ln.strip().rstrip(",") for ln in body.strip().splitlines()] == [f"pub {f}: u64" for f in ("capacity", "count", "entered", "evicted")]
+    assert rust_fields("TgWindowInfo") == [f"pub {f}: u64" for f in ("capacity", "count", "entered", "evicted")]
     assert "pub fn tg_window_absorb(e: *mut TgEngine, n_absorbed: *mut i32) -> c_int;" in rust
     assert ("pub fn tg_window_train(e: *mut TgEngine, first: c_int, count: c_int, seed: u64, mean_loss_p: *mut f32, mean_loss_z: *mut f32, "
             "steps: *mut i32) -> c_int;") in rust
@@ -147,11 +135,7 @@ def test_every_entry_point_fails_loudly_without_a_device_or_an_engine():
 
 
 def test_the_loop_script_takes_the_window_and_defaults_to_the_loop_as_it_was():
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    try:
-        import train_loop
-    finally:
-        sys.path.pop(0)
+    train_loop = script("train_loop")
     assert train_loop.parse_args([]).window == 0
     assert train_loop.parse_args(["--window", "4000"]).window == 4000
     with pytest.raises(SystemExit) as ei:
