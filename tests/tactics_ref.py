@@ -10,10 +10,12 @@ import functools
 
 import numpy as np
 
+import posgen
 from oracle import oracle
 
 TG_MAX_MOVES = 512
-VARIANTS = ("no_suicide", "draw_is_loss", "min_at_lost", "last_best", "no_early_stop")
+VARIANTS = ("no_suicide", "draw_is_loss", "min_at_lost", "last_best", "no_early_stop", "reversible_is_ongoing")
+TG_DRAW_REVERSIBLE = 6  # the result code of the 50-reversible-plies draw
 FIELDS = ("value", "best", "counts", "moves", "move_values")
 
 
@@ -48,7 +50,10 @@ class Ref:
         ch, status = oracle.play(self.n, S, moves)
         assert not status.any()
         self.nodes += len(ch)
-        return ch, oracle.result(self.n, ch)
+        res = oracle.result(self.n, ch)
+        if self.variant == "reversible_is_ongoing":  # the wrong result code tested: the draw by the counter is searched on
+            res = np.where(res == TG_DRAW_REVERSIBLE, 0, res).astype(res.dtype)
+        return ch, res
 
     def W(self, S, L):
         """some move wins at once, or leads to an ongoing position that is X within L - 1"""
@@ -198,6 +203,15 @@ SETS = {
     "s5_200": lambda: oracle.playouts(5, 200, 11, style=3)["prev"],
 }
 BOARD = {"p5_400": 5, "r5_400": 5, "p5_160": 5, "p6_200": 6, "p6_80": 6, "s5_200": 5}
+
+# the same positions one, two and three spreads away from the 50-reversible-plies draw (play-outs keep the counter far from 50):
+# "<base>_r<counter>" is a prefix of <base> with the header's reversible_plies overwritten
+REVERSIBLE = {"p5_400_r49": ("p5_400", 120, 49), "p5_400_r48": ("p5_400", 120, 48), "s5_200_r49": ("s5_200", 120, 49),
+              "s5_200_r48": ("s5_200", 120, 48), "p6_200_r49": ("p6_200", 60, 49), "p6_200_r48": ("p6_200", 60, 48),
+              "s5_200_r47": ("s5_200", 200, 47)}
+for _name, (_base, _rows, _r) in REVERSIBLE.items():
+    SETS[_name] = lambda b=_base, k=_rows, r=_r: posgen.with_header(positions(b)[:k], reversible_plies=r)
+    BOARD[_name] = BOARD[_base]
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,12 +1,13 @@
 """The forced-win reference (tests/tactics_ref.py) itself: hand-made positions with their values written out, the teeth of the
-comparison the GPU tests use (each planted mistake is rejected on one of their sets), and a recomputed sample of the committed
-depth-4 / depth-5 cases.  No GPU."""
+comparison the GPU tests use (each planted mistake is rejected on one of their sets; the two about draws on every set that puts the
+50-reversible-plies draw inside the tree), and a recomputed sample of the committed depth-4 / depth-5 / depth-6 cases.  No GPU."""
 import json
 import os
 
 import numpy as np
 import pytest
 
+import posgen
 import tactics_ref as T
 from oracle import oracle
 
@@ -72,7 +73,7 @@ def test_the_only_escape_is_a_draw():
     assert _solve(3, ptn, 2, variant="draw_is_loss")[0] == -2
 
 
-@pytest.mark.parametrize("variant", T.VARIANTS)
+@pytest.mark.parametrize("variant", ("no_suicide", "draw_is_loss", "min_at_lost", "last_best", "no_early_stop"))
 def test_the_comparison_rejects_a_planted_mistake(variant):
     """on the 400 playout positions at depth 3 with the early stop, one of the GPU tests' own comparisons (the early-stop variant on
     a prefix: it is the ALL_MOVES table, the expensive one)"""
@@ -85,9 +86,43 @@ def test_the_comparison_rejects_a_planted_mistake(variant):
     assert T.compare({f: good[f][:40] for f in T.FIELDS}, T.Ref(5).solve(T.positions("p5_400")[:40], 3, False)) == []
 
 
+def _reversible_depth(name):
+    return 4 if name.endswith("_r47") else 3
+
+
+@pytest.mark.parametrize("variant", ("reversible_is_ongoing", "draw_is_loss"))
+@pytest.mark.parametrize("name", sorted(T.REVERSIBLE))
+def test_the_reversible_sets_reject_a_mistake_about_the_draw(name, variant):
+    """the sets whose header counter stands at 49, 48 and 47: a solver that searches on through the 50-reversible-plies draw, or
+    takes it for a loss, is rejected by the GPU tests' comparison on every one of them (on the rows whose ALL_MOVES table the counter
+    changes, the first 3 of them: the planted solver is slow where it plays on)"""
+    base, k, _ = T.REVERSIBLE[name]
+    depth = _reversible_depth(name)
+    scan = k if base == "s5_200" else 24  # (the tall-stack sets move few rows and their references are cheap; the others move a third)
+    good, plain = T.reference(name, depth, True), T.Ref(T.BOARD[base]).solve(T.positions(base)[:scan], depth, True)
+    rows = np.nonzero((good["move_values"][:scan] != plain["move_values"]).any(axis=1))[0][:3]
+    assert len(rows) >= 2
+    bad = T.Ref(T.BOARD[name], variant).solve(T.positions(name)[rows], depth, True)
+    assert T.compare({f: good[f][rows] for f in T.FIELDS}, bad) != []
+    assert T.compare({f: good[f][rows] for f in T.FIELDS}, T.Ref(T.BOARD[name]).solve(T.positions(name)[rows], depth, True)) == []
+
+
+def test_playouts_alone_hardly_see_the_reversible_draw():
+    """the gap the sets above close.  On the 400 play-out positions at depth 3 with the early stop — the comparison the other planted mistakes are tried on — a
+    solver that searches on through the 50-reversible-plies draw differs in three move values of ONE position (row 115, whose play-out
+    happens to have brought the counter near 50): rejected, but by a single row, and on the tall-stack set not at all."""
+    good = T.reference("p5_400", 3, False)
+    bad = T.reference("p5_400", 3, False, "reversible_is_ongoing")
+    assert np.array_equal(good["value"], bad["value"]) and np.array_equal(good["best"], bad["best"])
+    rows, cols = np.nonzero(good["move_values"] != bad["move_values"])
+    assert rows.tolist() == [115, 115, 115]
+    assert int(posgen.header(T.positions("p5_400")[115:116], "reversible_plies")[0]) >= 47
+    assert T.compare(T.reference("s5_200", 3, False), T.reference("s5_200", 3, False, "reversible_is_ongoing")) == []  # the tall stacks: no tooth at all
+
+
 def test_the_committed_cases_are_the_reference():
     """a sample of tests/golden/solve_cases.json recomputed (make_solve_cases.py rebuilds all of it): one position of
-    each of the values +5, -4, +3 and +1"""
+    each of the values +5, -4, +3 and +1 at depth 4 and 5, one of -6 at depth 6 and one 6×6 position of +5 at depth 5"""
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solve_cases.json")) as f:
         doc = json.load(f)
     cases = doc["cases"]
@@ -104,3 +139,19 @@ def test_the_committed_cases_are_the_reference():
             value, best, moves, vals = ref.solve_one(states[c["index"]], depth, False)
             e = c[f"depth{depth}"]
             assert (value, best, [int(m) for m in moves], vals) == (e["value"], e["best"], c["moves"], e["move_values"]), (c["index"], depth)
+    # depth 6 and 6×6: one position of value -6 (a tall-stack one: the cheapest to recompute) and one 6×6 position of value +5
+    tall, six = doc["tall_stacks"], doc["six"]
+    assert tall["value_counts_depth5_first_100"] == {"-4": 1, "-2": 1, "0": 29, "1": 69} and len(tall["cases"]) == 29
+    assert six["value_counts_depth5_all_80"] == {"-4": 3, "-2": 3, "0": 16, "1": 52, "3": 2, "5": 4}
+    deep6 = [c["depth6"]["value"] for c in cases] + [c["depth6"]["value"] for c in tall["cases"]]
+    assert deep6.count(-6) == 3 and [c["index"] for c in tall["cases"] if c["depth6"]["value"] == -6] == [43, 99]
+    assert [c["index"] for c in cases if c["depth6"]["value"] == -6] == [44]
+    assert all(c["depth5"]["value"] == 0 for c in tall["cases"])
+    T.require_classes([c["depth5"]["value"] for c in six["cases"]], (1, -2, 3, -4, 5))
+    assert sum("depth6" in c for c in six["cases"]) == 9 + len(six["depth6_unproven"]) and len(six["depth6_unproven"]) <= 6
+    for block, depth, wanted in ((tall, 6, -6), (six, 5, 5)):
+        c = next(c for c in block["cases"] if c[f"depth{depth}"]["value"] == wanted)
+        n = T.BOARD[block["set"]]
+        value, best, moves, vals = T.Ref(n).solve_one(T.positions(block["set"])[c["index"]], depth, False)
+        e = c[f"depth{depth}"]
+        assert (value, best, [int(m) for m in moves], vals) == (e["value"], e["best"], c["moves"], e["move_values"]), (block["set"], c["index"])
