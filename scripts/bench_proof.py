@@ -7,7 +7,7 @@ for `--rounds` rounds because other people's work shares the host.
 
     parent   self-play on the parent commit's library (--parent-tree: a BUILT tree of that commit)
     off      this build, TG_PROOF_OFF (the default: the parent's kernels)
-    on       this build, TG_PROOF_ON: the selects of search_proof_kernels.hip and the proof-aware pick
+    on       this build, TG_PROOF_ON: the PROOF instantiations of the tree kernels (tree_kernels.hip) and of the pick
 The summary holds
     off_vs_parent   the two medians and the parent's own spread between its runs of this job ((max - min) / median): the margin
                     within which `off` has to agree with `parent`, and whether it does

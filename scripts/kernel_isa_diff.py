@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Did a change move any kernel?  Compare the device code of two source trees, kernel by kernel.
 
-    python scripts/kernel_isa_diff.py A B [--only tower_kernels.hip ...] [--jobs 8] [--show 20]
+    python scripts/kernel_isa_diff.py A B [--only tower_kernels.hip ...] [--jobs 8] [--show 20] [--pairs FILE]
 
 A and B are directories that hold tak_amd/csrc/, or git revisions of this repository (exported with `git archive` into a
 temporary directory; `.` and paths are taken as directories first).  Every tak_amd/csrc/*.hip of each tree is compiled
@@ -10,7 +10,8 @@ reads), disassembled and split per symbol with addresses and encodings dropped; 
 counts, LDS and private-segment size, ...) come from `llvm-readelf --notes`.  A symbol is compared wherever it lives: the two
 trees are paired by symbol name over all their compiled files, not per file name, so a kernel that moved to another translation
 unit is `same` if its text and descriptor are; the line names the file on both sides.  A symbol that one tree emits from two
-files is `twice`, a failure of its own.  What llvm-objdump prints behind a symbol's last instruction — the zero fill up to the next
+files is `twice`, a failure of its own.  A kernel that was renamed is paired through --pairs (a file of lines `OLD NEW`, mangled
+names): its line shows `OLD → NEW`.  What llvm-objdump prints behind a symbol's last instruction — the zero fill up to the next
 symbol's alignment (`...`), the s_nop / s_code_end padding behind the last symbol of .text — is dropped: it belongs to the symbol's
 place in its file, not to the kernel, and differs as soon as a kernel has another neighbour.  --only is applied per tree to the
 files that exist there.  Per symbol one line: same / differs / only in A / only in B / twice; then a summary line.  Exit status 0
@@ -134,10 +135,20 @@ def main():
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--show", type=int, default=0, help="lines of unified diff to print for a symbol that differs")
     ap.add_argument("--quiet", action="store_true", help="print only the symbols that are not `same`, and the summary")
+    ap.add_argument("--pairs", help="a file of lines `OLD NEW` (mangled names; `#` starts a comment): symbol OLD of A is compared with "
+                                    "symbol NEW of B, for kernels that were renamed")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="kernel_isa_diff_") as tmp:
         files_a, A, twice_a = build_tree(resolve_tree(args.a, tmp), os.path.join(tmp, "obj_a"), args.only, args.jobs)
         files_b, B, twice_b = build_tree(resolve_tree(args.b, tmp), os.path.join(tmp, "obj_b"), args.only, args.jobs)
+    was = {}  # NEW → OLD for the pairs that were applied: from here on A holds OLD's code under NEW's name
+    for line in open(args.pairs) if args.pairs else ():
+        pair = line.split("#")[0].split()
+        if len(pair) == 2 and pair[0] in A and pair[1] not in A:
+            was[pair[1]] = pair[0]
+            A[pair[1]] = A.pop(pair[0])
+            if pair[0] in twice_a:
+                twice_a[pair[1]] = twice_a.pop(pair[0])
     count = {"same": 0, "differs": 0, "only in A": 0, "only in B": 0, "twice": 0}
     kernels = 0
     for sym in sorted(set(A) | set(B)):
@@ -163,7 +174,8 @@ def main():
         kernels += (sym in A and A[sym][2] is not None) or (sym in B and B[sym][2] is not None)
         if verdict != "same" or not args.quiet:
             where = fa if fa == fb else f"{fa} → {fb}" if fa and fb else fa or fb
-            print(f"{verdict:9s} {where} {sym}" + (": " + "; ".join(what) if what else ""))
+            name = f"{was[sym]} → {sym}" if sym in was else sym
+            print(f"{verdict:9s} {where} {name}" + (": " + "; ".join(what) if what else ""))
         if verdict == "differs" and args.show:
             for line in list(difflib.unified_diff(A[sym][1], B[sym][1], "A", "B", lineterm="", n=2))[: args.show]:
                 print("    " + line)

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Where k_backup_select spends its time: runs a few plies of C2 self-play on a library built with -DTG_TREE_STAMPS
-(search_kernels.hip; TAKGPU_LIB points at it) and prints, for the waves of games 0..63 in the last iteration, the mean
+(tree_kernels.hip; TAKGPU_LIB points at it) and prints, for the waves of games 0..63 in the last iteration, the mean
 s_memtime deltas between the phase boundaries.  Every stamp waits for the wave's outstanding memory operations, so the
 deltas attribute latency to phases; their sum is somewhat longer than the undisturbed kernel.
-    make -C tak_amd/csrc && hipcc … -DTG_TREE_STAMPS -c search_kernels.hip …; TAKGPU_LIB=… python scripts/probes/tree_stamps.py"""
+    make -C tak_amd/csrc && hipcc … -DTG_TREE_STAMPS -c tree_kernels.hip …; TAKGPU_LIB=… python scripts/probes/tree_stamps.py"""
 import ctypes as C
 import os
 import sys

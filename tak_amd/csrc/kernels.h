@@ -213,17 +213,17 @@ hipError_t launch_adam(hipStream_t st, float* p, const float* g, float* m, float
                        float wd, float bc1, float bc2_sqrt, float gscale);
 hipError_t launch_sum_rows(hipStream_t st, const float* rows, int n, double* out);
 
-// search_kernels.hip
 struct SearchDev;
 struct SelfPlayDev;
 struct DebugOut;
-void launch_select(hipStream_t st, const SearchDev& S, const uint8_t* active);
-void launch_backup(hipStream_t st, const SearchDev& S);
-void launch_backup_select(hipStream_t st, const SearchDev& S);  // backup of iteration i + select of iteration i+1 (all S.batch passes of each)
-// search_list_kernels.hip: the same three over a compacted list of `count` games (wave w serves list[w], leaf slots w·batch + pass, grid sized from count)
-void launch_select_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count);
-void launch_backup_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count);
-void launch_backup_select_list(hipStream_t st, const SearchDev& S, const int32_t* list, int count);
+// tree_kernels.hip: one wave per game.  list = null: over the S.G games, wave → game by identity; else over a compacted list of
+// `count` games (wave w serves list[w], leaf slots w·batch + pass, grid sized from count).  active (optional): a mask over games.
+// proof: the selects with the solver backup (TG_PROOF_ON); the backup alone knows nothing of proofs
+void launch_select(hipStream_t st, const SearchDev& S, const uint8_t* active, const int32_t* list, int count, bool proof);
+void launch_backup(hipStream_t st, const SearchDev& S, const int32_t* list, int count);
+// backup of iteration i + select of iteration i+1 (all S.batch passes of each)
+void launch_backup_select(hipStream_t st, const SearchDev& S, const int32_t* list, int count, bool proof);
+// search_kernels.hip
 void launch_dirichlet(hipStream_t st, const SearchDev& S, const uint8_t* active, float alpha, float ratio);
 void launch_apply_noise(hipStream_t st, const SearchDev& S, const uint8_t* active, const float* noise, float ratio);
 void launch_reroot(hipStream_t st, const SearchDev& S, const int32_t* op);
@@ -236,16 +236,11 @@ void launch_sp_opening(hipStream_t st, const SearchDev& S);
 void launch_sp_instant_win(hipStream_t st, const SearchDev& S, const SelfPlayDev& P);
 void launch_sp_finish(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, int32_t* op);
 void launch_sp_noise_mask(hipStream_t st, const SearchDev& S, const SelfPlayDev& P);
-void launch_sp_pick(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, int32_t* op);
-// (search_list_kernels.hip) the ascending list of the games owed a ply's boosted iterations, and their count
+void launch_sp_pick(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, int32_t* op, bool proof);  // proof: the proof-aware pick (TG_PROOF_ON)
+// the ascending list of the games owed a ply's boosted iterations, and their count
 void launch_sp_boost_list(hipStream_t st, const SearchDev& S, int boost_plies, int32_t* list, int32_t* count);
 void launch_sp_count_ply(hipStream_t st, const SelfPlayDev& P);
-// search_proof_kernels.hip (TG_PROOF_ON): the selects with the solver backup — list = null: over S.G games and the mask, else over
-// the compacted list —, the roots' statuses for tg_search_proof, the proof-aware pick of self-play
-void launch_select_proof(hipStream_t st, const SearchDev& S, const uint8_t* active, const int32_t* list, int count);
-void launch_backup_select_proof(hipStream_t st, const SearchDev& S, const int32_t* list, int count);
-void launch_proof_read(hipStream_t st, const SearchDev& S, uint8_t* root_status, uint8_t* child_status, int32_t* counts);
-void launch_sp_pick_proof(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, int32_t* op);
+void launch_proof_read(hipStream_t st, const SearchDev& S, uint8_t* root_status, uint8_t* child_status, int32_t* counts);  // the roots' statuses for tg_search_proof
 
 // symm_kernels.hip: the dihedral symmetries at the evaluation (tg_policy_eval_symm) and in the search (TG_SYMM_HASHED)
 // perm[8][P]: perm[s][j] = policy slot of the image under s of the move whose slot is j; the caller fills it with −1 first

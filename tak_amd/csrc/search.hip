@@ -260,14 +260,15 @@ struct GatherScope {
 //   list given:      the same over the compacted list of `count` games (0 < count < G): wave w serves list[w], leaf slots
 //                    w·batch + pass, the network on count × batch leaves
 //   TG_SYMM_HASHED:  one more kernel in front of every `net` (k_symm_leaves over the iteration's leaf slots); off: none
-//   TG_PROOF_ON:     the same schedule with the selects of search_proof_kernels.hip; the backups are the same kernels
+//   TG_PROOF_ON:     the same schedule with the PROOF instantiations of the selects; the backups are the same kernels
 int search_iterate(TgEngine* e, int iters, const uint8_t* d_active, const int32_t* list, int count) {
     Search* s = e->search;
     if (iters <= 0 || (list && count <= 0)) return TG_OK;
     const int leaves = (list ? count : s->d.G) * s->d.batch;
     bind_logits(e, leaves);
     GatherScope scope{e};
-    if (s->proof) s->proof_ran = true;
+    const bool proof = s->proof != 0;
+    if (proof) s->proof_ran = true;
     SearchDev d = s->d;
     d.pass = d.batch > 1 ? -1 : 0;  // -1: the kernel runs the `batch` passes of a game back to back in that game's wave
     hipStream_t st = e->stream;
@@ -278,11 +279,7 @@ int search_iterate(TgEngine* e, int iters, const uint8_t* d_active, const int32_
         if (d.planes) { d.planes = nullptr; d.leaf_state = s->leaf_state.as<uint8_t>(); }
     }
     for (int i = 0; i < iters; i++) {
-        if (i == 0 || d_active) {
-            if (s->proof) launch_select_proof(st, d, d_active, list, count);
-            else if (list) launch_select_list(st, d, list, count);
-            else launch_select(st, d, d_active);
-        }
+        if (i == 0 || d_active) launch_select(st, d, d_active, list, count, proof);
         if (e->cfg.evaluator == TG_EVAL_RESNET) {
             if (symm) { if (int rc = symm_search_leaves(e, d, leaves); rc) return rc; }
             float* pol = d.logits ? nullptr : d.policy;  // logits mode: the backup takes softmax / tanh itself
@@ -290,9 +287,8 @@ int search_iterate(TgEngine* e, int iters, const uint8_t* d_active, const int32_
             if (rc) return rc;
         }
         const bool last = d_active || i + 1 == iters;  // (nothing follows, or the next select needs the mask)
-        if (!last && s->proof) launch_backup_select_proof(st, d, list, count);
-        else if (list) last ? launch_backup_list(st, d, list, count) : launch_backup_select_list(st, d, list, count);
-        else last ? launch_backup(st, d) : launch_backup_select(st, d);
+        if (last) launch_backup(st, d, list, count);
+        else launch_backup_select(st, d, list, count, proof);
     }
     TG_HIP(hipGetLastError());
     return TG_OK;

@@ -40,7 +40,7 @@ struct Search {
     DevBuf st_hdr, st_state, st_moves, st_visits, st_count, out_hdr, out_state, out_moves, out_visits, fin, recycle, out_off, chosen,
         mask, stats;
     unsigned long long drained = 0, dropped = 0;
-    int proof = 0;  // tg_search_set_proof: TG_PROOF_ON = the selects and the self-play pick of search_proof_kernels.hip
+    int proof = 0;  // tg_search_set_proof: TG_PROOF_ON = the PROOF instantiations of the selects and of the self-play pick
     bool proof_ran = false;  // iterations have run under TG_PROOF_ON since the trees were last reset: they may hold TG_PROVEN_* codes
     DevBuf p_root, p_child, p_counts;  // tg_search_proof
     DevBuf re_status;                  // tg_reanalyse: one status byte per row of the call's range

@@ -1,6 +1,7 @@
-// search_kernels.hip — GPU-resident MCTS (one wavefront per game) and the self-play driver kernels.
+// search_kernels.hip — GPU-resident MCTS (one wavefront per game): everything around the tree passes, and the self-play driver
+// kernels.  The passes themselves (select, backup and their fused hand-overs) are tree_kernels.hip's.
 //
-// Replaces reference alpha-tak/src/search/mcts.rs (virtual_rollout :26-65, select :94-118,
+// With tree_pass.cuh and tree_kernels.hip, replaces reference alpha-tak/src/search/mcts.rs (virtual_rollout :26-65, select :94-118,
 // devirtualize_path :67-91, update_concrete :120-124), search/noise.rs, search/play.rs and the
 // per-ply phases of train/src/self_play.rs:108-259.  The float arithmetic of PUCT and of the value
 // backup is written in the reference's operation order and compiled with -ffp-contract=off, the
@@ -15,7 +16,6 @@
 #include "search.cuh"
 #include "softmax.cuh"
 #include "tree_pass.cuh"
-#include "tree_launch.h"
 
 namespace tg {
 
@@ -26,101 +26,6 @@ __global__ void k_pool_publish(SearchDev S) {
     const unsigned long long owned = S.pool_ctl[0] - (S.pool_ctl[2] - (unsigned long long)(S.n_chunks - 1));
     if (owned > S.pool_ctl[3]) S.pool_ctl[3] = owned;
     S.pool_ctl[2] = S.pool_ctl[1];
-}
-
-// One wave per game.  S.pass ≥ 0: that one virtual rollout; S.pass < 0: all `batch` virtual rollouts of the iteration one after
-// the other — a game's tree is only ever touched by its own wave, so the passes need no kernel boundary between them, only
-// the wave's own stores ordered before its later loads (s_waitcnt: a wave's accesses go through one in-order, write-through
-// L1 path; an agent-scope fence would write back the whole L2 per wave and cost more than the launches it replaces).
-template <int NB>
-__global__ __launch_bounds__(WPB * 64) void k_select(SearchDev S, const uint8_t* __restrict__ active) {
-    __shared__ uint32_t path_lds[WPB][MAX_DEPTH];
-    __shared__ uint16_t mv_lds[WPB][EX_MOVES];
-    const int g = game_of_wave();
-    if (g >= S.G) return;
-    uint32_t* path = path_lds[threadIdx.x >> 6];
-    const int p0 = S.pass < 0 ? 0 : S.pass, p1 = S.pass < 0 ? S.batch : S.pass + 1;
-    for (int p = p0; p < p1; p++) {
-        select_pass<NB>(S, active, g, p, path, mv_lds[threadIdx.x >> 6]);
-        if (p + 1 < p1) wave_sync_mem();
-    }
-}
-
-// S.pass as in k_select: one de-virtualisation, or all of the iteration's in rollout order
-template <int NB>
-__global__ __launch_bounds__(WPB * 64) void k_backup(SearchDev S) {
-    const int g = game_of_wave();
-    if (g >= S.G) return;
-    const int p0 = S.pass < 0 ? 0 : S.pass, p1 = S.pass < 0 ? S.batch : S.pass + 1;
-    for (int p = p0; p < p1; p++) {
-        backup_pass<NB>(S, g, p, S.root[g]);
-        if (p + 1 < p1) wave_sync_mem();
-    }
-}
-
-// De-virtualise iteration i and select the leaf of iteration i + 1 in one launch (one leaf per game): the two touch the same
-// few nodes of the same tree from the same wave, so the second finds them in cache and one kernel boundary per iteration
-// disappears.  Same device functions as the separate kernels → same trees.
-template <int NB>
-__global__ __launch_bounds__(WPB * 64) void k_backup_select(SearchDev S) {
-    __shared__ uint32_t path_lds[WPB][MAX_DEPTH];
-    __shared__ uint16_t mv_lds[WPB][EX_MOVES];
-    const int g = game_of_wave();
-    if (g >= S.G) return;
-    TG_TSTAMP(g, 0);
-    // what the select needs of the root and the backup does not write is requested before the backup: the root's index, its
-    // cold record and the packed root position arrive under the backup's own round trips
-    // (requested, none of them waited for: the first wait is inside the backup, behind its own independent requests)
-    RootPre pre;
-    const uint32_t root_v = S.root[g];
-    const Geom geo = make_geom(NB ? NB : S.n);
-    pre.raw = ws_load_raw(S.root_state + (size_t)g * geo.bytes, geo);
-    pre.alive_v = (uint32_t)S.alive[g];
-    pre.abort_v = (uint32_t)S.abort[g];
-    pre.on = true;
-    backup_pass<NB>(S, g, 0, root_v, &pre);
-    wave_sync_mem();
-    TG_TSTAMP(g, 3);  // path updated
-    select_pass<NB>(S, nullptr, g, 0, path_lds[threadIdx.x >> 6], mv_lds[threadIdx.x >> 6], pre);
-    TG_TSTAMP(g, 31);
-}
-
-// The same for `batch` > 1 virtual rollouts per tree and iteration (Player's batching, player.rs:77-110): the iteration's
-// de-virtualisations in rollout order, then the next iteration's virtual rollouts, all in the game's wave — what k_backup
-// followed by k_select do in two launches, on the same device functions → same trees.  A kernel of its own, so that the
-// one-leaf k_backup_select keeps its straight-line form.  Between passes the wave's stores are ordered before its later loads
-// by s_waitcnt alone (see k_select).
-// Root hand-over: the root's index, packed position and the alive / abort flags are requested before the first backup (no
-// backup writes them) and consumed by the first select; the root's cold record and its (visits, virtual) come from the LAST
-// backup only — every earlier view of them is stale once a later pass has de-virtualised through the root.  The selects
-// after the first read everything afresh: a pass that retires the game (limit_hit) sets S.abort[g], which the following
-// passes must see to mark their slots skipped (leaf_kind 0: the next backup leaves them alone, and their network rows keep
-// the finite contents of an earlier leaf).
-template <int NB>
-__global__ __launch_bounds__(WPB * 64) void k_backup_select_batch(SearchDev S) {
-    __shared__ uint32_t path_lds[WPB][MAX_DEPTH];
-    __shared__ uint16_t mv_lds[WPB][EX_MOVES];
-    const int g = game_of_wave();
-    if (g >= S.G) return;
-    RootPre pre;
-    const uint32_t root_v = S.root[g];
-    const Geom geo = make_geom(NB ? NB : S.n);
-    pre.raw = ws_load_raw(S.root_state + (size_t)g * geo.bytes, geo);
-    pre.alive_v = (uint32_t)S.alive[g];
-    pre.abort_v = (uint32_t)S.abort[g];
-    pre.on = true;
-    const int B = S.batch;
-    for (int p = 0; p < B; p++) {
-        backup_pass<NB>(S, g, p, root_v, p + 1 == B ? &pre : nullptr);
-        wave_sync_mem();
-    }
-    uint32_t* path = path_lds[threadIdx.x >> 6];
-    uint16_t* mvl = mv_lds[threadIdx.x >> 6];
-    for (int p = 0; p < B; p++) {
-        select_pass<NB>(S, nullptr, g, p, path, mvl, pre);
-        pre.on = false;
-        if (p + 1 < B) wave_sync_mem();
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -581,7 +486,56 @@ __global__ void k_sp_noise_mask(SearchDev S, SelfPlayDev P) {
     P.mask[g] = (S.alive[g] && (int)(hdr[0] >> 16) < P.noise_plies) ? 1 : 0;
 }
 
+// The games owed the boosted iterations of this ply (QUAD_ROLLOUT_PLIES, train/src/self_play.rs:19,63): alive, not retired by
+// this ply's search so far, root ply < boost_plies — in ascending order, with their count.  One workgroup: every thread counts its
+// run of consecutive games, an inclusive scan places the runs (as k_sp_finish_scan does).
+__global__ __launch_bounds__(1024) void k_sp_boost_list(SearchDev S, int boost_plies, int32_t* __restrict__ list, int32_t* __restrict__ count) {
+    __shared__ uint32_t s_n[1024];
+    const int tid = threadIdx.x;
+    const int per = (S.G + 1023) / 1024;
+    const int g0 = min(tid * per, S.G), g1 = min(g0 + per, S.G);
+    const Geom geo = make_geom(S.n);
+    auto owed = [&](int g) {
+        const uint32_t* hdr = (const uint32_t*)(S.root_state + (size_t)g * geo.bytes + geo.bytes - 16);
+        return S.alive[g] && !S.abort[g] && (int)(hdr[0] >> 16) < boost_plies;
+    };
+    uint32_t n = 0;
+    for (int g = g0; g < g1; g++) n += owed(g) ? 1u : 0u;
+    s_n[tid] = n;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {  // Hillis–Steele inclusive scan
+        const uint32_t a = tid >= d ? s_n[tid - d] : 0u;
+        __syncthreads();
+        s_n[tid] += a;
+        __syncthreads();
+    }
+    uint32_t o = s_n[tid] - n;  // ≤ g0: the list never holds more entries than games
+    for (int g = g0; g < g1; g++)
+        if (owed(g)) list[o++] = g;
+    if (tid == 1023) *count = (int32_t)s_n[1023];
+}
+
+// tg_search_proof: the raw result nibble of every root and of its children, in possible_moves order; zero past the child count
+__global__ __launch_bounds__(64) void k_proof_read(SearchDev S, uint8_t* __restrict__ root_status, uint8_t* __restrict__ child_status,
+                                                   int32_t* __restrict__ counts) {
+    const int g = blockIdx.x;
+    const int lane = threadIdx.x;
+    const NodeCold rc = S.cold[S.root[g]];
+    const uint32_t nchild = min((uint32_t)rc.nres & 0xfffu, (uint32_t)EX_MOVES), cb = rc.child;
+    if (lane == 0) { root_status[g] = (uint8_t)(rc.nres >> 12); counts[g] = (int32_t)nchild; }
+    for (uint32_t i = lane; i < (uint32_t)EX_MOVES; i += 64)
+        child_status[(size_t)g * EX_MOVES + i] = i < nchild ? (uint8_t)(S.cold[cb + i].nres >> 12) : (uint8_t)0;
+}
+
 // (e) pick_move (play.rs:49-67), example (:222-225), play (:227-228), result (:230)
+// PROOF (tg_search_set_proof(TG_PROOF_ON); no counterpart in the reference): the candidates are narrowed by the root children's
+// statuses.  m = the root's colour to move.
+//   1. some child decided for m: among those children the most visited, the LAST on ties — whatever the temperature
+//   2. otherwise the candidates are the children not decided for the opponent (all children if that leaves none), and on them
+//      pick_move: exploit → most visited, last on ties; explore → the RNG_PICK draw over the visits with the excluded children's
+//      visits taken as 0; candidates without a visit → exploit over the candidates (not ERRF_PICK)
+// The example keeps the root's real visits.  PROOF off: every child is a candidate, none of the narrowing is compiled.
+template <bool PROOF>
 __global__ __launch_bounds__(WPB * 64) void k_sp_pick(SearchDev S, SelfPlayDev P, int32_t* __restrict__ op) {
     const int g = game_of_wave();
     if (g >= S.G) return;
@@ -601,12 +555,49 @@ __global__ __launch_bounds__(WPB * 64) void k_sp_pick(SearchDev S, SelfPlayDev P
     uint8_t* st = S.root_state + (size_t)g * geo.bytes;
     ws_load(s, st, geo);
     if (nchild == 0) { flag(S, ERRF_PICK); return; }
+    const uint32_t m = s.to_move, opp = m ^ 1u;
+    bool step1 = false, narrow = false;
+    if constexpr (PROOF) {
+        bool any_m = false, any_open = false;
+        for (uint32_t i = lane; i < nchild; i += 64) {
+            const uint32_t cs = proof_status((uint32_t)cold[cb + i].nres >> 12);
+            any_m |= cs == m;
+            any_open |= cs != opp;
+        }
+        step1 = __ballot(any_m) != 0;
+        narrow = __ballot(any_open) != 0;
+    }
+    auto candidate = [&](uint32_t i) {
+        if constexpr (PROOF) {
+            const uint32_t cs = proof_status((uint32_t)cold[cb + i].nres >> 12);
+            return step1 ? cs == m : narrow ? cs != opp : true;
+        } else return true;
+    };
+    auto visits_of_candidates = [&]() {
+        unsigned long long total = 0;
+        for (uint32_t i = lane; i < nchild; i += 64) total += candidate(i) ? hot[cb + i].visits : 0u;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            unsigned long long o = ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(total >> 32), d) << 32) |
+                                   (uint32_t)__shfl_xor((int)(uint32_t)total, d);
+            total += o;
+        }
+        return total;
+    };
+    // PROOF: the total decides the branch (no visit on a candidate → exploit); off: it is taken on the explore branch only
+    unsigned long long total = 0;
+    bool exploit = (int)s.ply >= P.exploit_plies;
+    if constexpr (PROOF) {
+        total = visits_of_candidates();
+        exploit = step1 || total == 0 || exploit;
+    }
     int pick = -1;
-    if ((int)s.ply >= P.exploit_plies) {
-        // max_by_key: most visits, last on ties
+    if (exploit) {
+        // max_by_key over the candidates: most visits, last on ties
         uint32_t bv = 0;
         int bi = -1;
         for (uint32_t i = lane; i < nchild; i += 64) {
+            if (!candidate(i)) continue;
             uint32_t v = hot[cb + i].visits;
             if (bi < 0 || v >= bv) { bv = v; bi = (int)i; }
         }
@@ -616,33 +607,37 @@ __global__ __launch_bounds__(WPB * 64) void k_sp_pick(SearchDev S, SelfPlayDev P
             int oi = __shfl_xor(bi, d);
             if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi > bi))) { bv = ov; bi = oi; }
         }
-        pick = bi;
+        pick = bi;  // (≥ 0: there is always a candidate)
     } else {
-        // WeightedIndex over visits with one RNG_PICK draw
-        unsigned long long total = 0;
-        for (uint32_t i = lane; i < nchild; i += 64) total += hot[cb + i].visits;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            unsigned long long o = ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(total >> 32), d) << 32) |
-                                   (uint32_t)__shfl_xor((int)(uint32_t)total, d);
-            total += o;
+        // WeightedIndex over the candidates' visits with one RNG_PICK draw
+        if constexpr (!PROOF) {
+            total = visits_of_candidates();
+            if (total == 0) { flag(S, ERRF_PICK); return; }
         }
-        if (total == 0) { flag(S, ERRF_PICK); return; }
         U4 r = rng_draw(S.seed, S.slot_base + (uint32_t)g, S.generation[g], s.ply, RNG_PICK, 0, 0);
         unsigned long long x = ((unsigned long long)r.v[0] << 32) | r.v[1];
         unsigned long long target = __umul64hi(x, total);
         unsigned long long carry = 0;
-        for (uint32_t i0 = 0; i0 < nchild && pick < 0; i0 += 64) {
+        // where a draw that no prefix exceeds ends: the last child, or (PROOF) the last candidate with visits
+        int last = (int)nchild - 1;
+        if constexpr (PROOF) last = -1;
+        for (uint32_t i0 = 0; i0 < nchild && (PROOF || pick < 0); i0 += 64) {
             uint32_t i = i0 + lane;
-            int v = i < nchild ? (int)hot[cb + i].visits : 0;
+            int v = (i < nchild && candidate(i)) ? (int)hot[cb + i].visits : 0;
             int incl = wave_inclusive_scan(v);
-            uint64_t bb = __ballot(i < nchild && carry + (unsigned long long)incl > target);
-            if (bb) pick = (int)i0 + __builtin_ctzll(bb);
+            uint64_t bb = __ballot(i < nchild && (!PROOF || v > 0) && carry + (unsigned long long)incl > target);
+            if (bb && pick < 0) pick = (int)i0 + __builtin_ctzll(bb);
+            if constexpr (PROOF) {
+                uint64_t nz = __ballot(v > 0);
+                if (nz) last = (int)i0 + 63 - __builtin_clzll(nz);
+            }
             carry += (unsigned long long)__shfl(incl, 63);
         }
-        if (pick < 0) pick = (int)nchild - 1;
+        if (pick < 0) pick = last;
     }
-    // example = (game before the move, visit counts of every child)
+    if constexpr (PROOF)
+        if (pick < 0 || (uint32_t)pick >= nchild) { flag(S, ERRF_PICK); return; }  // (cannot happen; never index out of the block)
+    // example = (game before the move, the REAL visit counts of every child)
     int slot;
     stage_example(S, P, g, s, geo, nchild, slot);
     if (slot < 0) {  // the game is past max_game_plies
@@ -670,12 +665,6 @@ __global__ __launch_bounds__(WPB * 64) void k_sp_pick(SearchDev S, SelfPlayDev P
 __global__ void k_sp_count_ply(SelfPlayDev P) { P.stats[ST_PLIES] += 1; }
 
 // ---- launchers --------------------------------------------------------------------------------
-void launch_select(hipStream_t st, const SearchDev& S, const uint8_t* active) { TG_BY_BOARD(k_select, S.G, S, active); }
-void launch_backup(hipStream_t st, const SearchDev& S) { TG_BY_BOARD(k_backup, S.G, S); }
-void launch_backup_select(hipStream_t st, const SearchDev& S) {
-    if (S.batch > 1) TG_BY_BOARD(k_backup_select_batch, S.G, S);
-    else TG_BY_BOARD(k_backup_select, S.G, S);
-}
 void launch_dirichlet(hipStream_t st, const SearchDev& S, const uint8_t* active, float alpha, float ratio) {
     hipLaunchKernelGGL(k_dirichlet, dim3(S.G), dim3(64), 0, st, S, active, alpha, ratio);
 }
@@ -707,15 +696,16 @@ void launch_sp_finish(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, 
 void launch_sp_noise_mask(hipStream_t st, const SearchDev& S, const SelfPlayDev& P) {
     hipLaunchKernelGGL(k_sp_noise_mask, dim3((S.G + 255) / 256), dim3(256), 0, st, S, P);
 }
-void launch_sp_pick(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, int32_t* op) {
-    hipLaunchKernelGGL(k_sp_pick, wgrid(S.G), dim3(WPB * 64), 0, st, S, P, op);
+void launch_sp_pick(hipStream_t st, const SearchDev& S, const SelfPlayDev& P, int32_t* op, bool proof) {
+    if (proof) hipLaunchKernelGGL(k_sp_pick<true>, wgrid(S.G), dim3(WPB * 64), 0, st, S, P, op);
+    else hipLaunchKernelGGL(k_sp_pick<false>, wgrid(S.G), dim3(WPB * 64), 0, st, S, P, op);
+}
+void launch_sp_boost_list(hipStream_t st, const SearchDev& S, int boost_plies, int32_t* list, int32_t* count) {
+    hipLaunchKernelGGL(k_sp_boost_list, dim3(1), dim3(1024), 0, st, S, boost_plies, list, count);
+}
+void launch_proof_read(hipStream_t st, const SearchDev& S, uint8_t* root_status, uint8_t* child_status, int32_t* counts) {
+    hipLaunchKernelGGL(k_proof_read, dim3(S.G), dim3(64), 0, st, S, root_status, child_status, counts);
 }
 void launch_sp_count_ply(hipStream_t st, const SelfPlayDev& P) { hipLaunchKernelGGL(k_sp_count_ply, dim3(1), dim3(1), 0, st, P); }
-
-#ifdef TG_TREE_STAMPS
-extern "C" int tg_debug_tree_stamps(unsigned long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tree_stamps), sizeof(g_tree_stamps));
-}
-#endif
 
 }  // namespace tg

@@ -155,8 +155,7 @@ int tg_selfplay_step(TgEngine* e, int plies) {
             }
             if (rc) return rc;
         }
-        if (s->proof) launch_sp_pick_proof(st, s->d, s->p, op);        // (e) with the proof-aware pick (takgpu.h)
-        else launch_sp_pick(st, s->d, s->p, op);                       // (e) :212-258
+        launch_sp_pick(st, s->d, s->p, op, s->proof != 0);             // (e) :212-258; TG_PROOF_ON: the proof-aware pick (takgpu.h)
         launch_sp_finish(st, s->d, s->p, op);
         launch_reroot(st, s->d, op);
         launch_sp_count_ply(st, s->p);

@@ -1,5 +1,5 @@
 // softmax.cuh — the reduction order of the policy softmax, shared by k_softmax (fc_kernels.hip: one 256-thread block per
-// position) and the tree backup (search_kernels.hip: one wave per game computes the same statistics from the logits, so
+// position) and the tree backup (backup_pass, tree_pass.cuh: one wave per game computes the same statistics from the logits, so
 // the probabilities never go through HBM).  Both must return the same BITS: a host-side MCTS (the narrow seam, the parity
 // tests) builds its trees from tg_policy_eval's probabilities, the engine from the in-kernel ones.
 #pragma once

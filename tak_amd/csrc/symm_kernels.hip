@@ -7,7 +7,6 @@
 //   k_symm_fold     policy[i][j] = (Σ_s p_s[i][perm[s][j]]) · (1/k), eval[i] = (Σ_s v_s[i]) · (1/k), ascending s;
 //   k_symm_leaves   one wave per leaf slot of a search iteration: the leaf's state → its image under the hashed s, the
 //                   children's policy indices → perm[s] of them.
-#undef TG_TREE_STAMPS  // the stamp buffer belongs to search_kernels.hip
 #include "symm.cuh"
 #include "tree_pass.cuh"  // ws_hash: the one statement of the state hash
 

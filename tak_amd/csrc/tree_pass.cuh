@@ -1,8 +1,9 @@
 // tree_pass.cuh — the two device functions every tree kernel is made of, and what they need: the virtual rollout of one leaf
 // (select_pass: virtual_rollout + select, mcts.rs:26-65,94-118) and its de-virtualisation (backup_pass: devirtualize_path,
-// mcts.rs:67-91), the node pool's take / give, the wave helpers.  Included by search_kernels.hip (one wave per game, wave → game
-// by identity) and search_list_kernels.hip (wave → game through a compacted list): the same operations on a game's tree in the
-// same order from both, so the trees are the same bit for bit; and by search_proof_kernels.hip, both mappings with PROOF = true.
+// mcts.rs:67-91), the node pool's take / give, the wave helpers.  tree_kernels.hip wraps the two in its four kernel templates
+// (wave → game by identity or through a compacted list, with or without proven values): the same operations on a game's tree in
+// the same order from every instantiation, so the trees are the same bit for bit.  search_kernels.hip and symm_kernels.hip use
+// the pool and the helpers.
 #pragma once
 #include <stdlib.h>
 
@@ -20,6 +21,7 @@ namespace tg {
 constexpr int WPB = TG_WPB;  // waves (games) per block (4: 256 threads; other values: scripts/probes/tree_wpb_probe.sh)
 
 __device__ inline int game_of_wave() { return (int)(blockIdx.x * WPB + (threadIdx.x >> 6)); }
+static inline dim3 wgrid(int waves) { return dim3((waves + WPB - 1) / WPB); }  // the grid of a one-wave-per-game launch
 __device__ inline void flag(const SearchDev& S, uint32_t bit) { atomicOr(S.err, bit); }
 // A game ran into one of the fixed capacities (TG_LIMIT_*, takgpu.h).  Self-play retires that game alone — the bit is kept
 // per game, its wave stops touching the tree, and the end of the ply discards its examples and restarts the slot;
@@ -30,18 +32,9 @@ __device__ inline void limit_hit(const SearchDev& S, int g, uint32_t bit) {
 }
 __device__ inline void wave_sync_mem() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
 
-// Diagnostic build only (-DTG_TREE_STAMPS, scripts/probes/tree_stamps.py): s_memtime stamps of the waves of the first 64 games
-// at the phase boundaries of k_backup_select; tg_debug_tree_stamps copies them out.  The product build compiles none of it.
-#ifdef TG_TREE_STAMPS
-__device__ unsigned long long g_tree_stamps[64][32];
-#define TG_TSTAMP(g, slot)                                                                                    \
-    do {                                                                                                      \
-        if ((g) < 64 && (slot) < 32 && (threadIdx.x & 63) == 0) {                                             \
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                        \
-            g_tree_stamps[(g)][(slot)] = __builtin_amdgcn_s_memtime();                                        \
-        }                                                                                                     \
-    } while (0)
-#else
+// The phase stamps of the diagnostic build: tree_kernels.hip defines the macro (and owns the buffer) under -DTG_TREE_STAMPS
+// before it includes this file; everywhere else, and in the product build, they are nothing.
+#ifndef TG_TSTAMP
 #define TG_TSTAMP(g, slot) do { } while (0)
 #endif
 
@@ -91,7 +84,7 @@ __device__ inline void update_concrete(NodeHot& h, float reward) {
     h.q = (cumulative + reward) / (float)h.visits;
 }
 
-// self-play (k_sp_instant_win, k_sp_pick and its proof-aware twin): reserves the next staging slot of game g and writes header +
+// self-play (k_sp_instant_win, k_sp_pick): reserves the next staging slot of game g and writes header +
 // state; returns the slot (or -1)
 __device__ inline void stage_example(const SearchDev& S, const SelfPlayDev& P, int g, const WState& s, const Geom& geo,
                                      uint32_t nmoves, int& slot_out) {
@@ -180,9 +173,9 @@ struct RootPre {
     uint32_t alive_v = 1, abort_v = 0;  // S.alive[g], S.abort[g] (neither changes between the request and the select)
 };
 
-// LIST: the wave serves an entry of a compacted list of games (the k_*_list kernels below): everything of the tree and the game
+// LIST: the wave serves an entry of a compacted list of games (tree_kernels.hip): everything of the tree and the game
 // is game g's, the leaf slot is the LIST POSITION w's — w·batch + p — so that the network sees a dense batch of the listed games.
-// PROOF: the MCTS-solver backup (tg_search_set_proof, search_proof_kernels.hip): a rollout that has just initialised a terminal
+// PROOF: the MCTS-solver backup (tg_search_set_proof): a rollout that has just initialised a terminal
 // node draws the conclusion for its ancestors (proof_walk above), a rollout that ends on a proven node backs its colour up like
 // a terminal's.  false: none of it is compiled.
 template <int NB, bool LIST = false, bool PROOF = false>
@@ -457,7 +450,7 @@ __device__ __forceinline__ void select_pass(const SearchDev& S, const uint8_t* _
 // path entry); the second round is the gather of the children's logits and the path nodes' records; then the stores.  Round 2
 // walked path → leaf → children's moves → index table → logits, five dependent round trips (19 k of the wave's 56 k cycles).
 // Returns through `pre` the root's (visits, virtual) as this backup leaves them, for the select that follows in the same launch.
-// `g` only names the leaf slots (g·batch + pass); the tree comes in through root_v.  The k_*_list kernels pass the list position.
+// `g` only names the leaf slots (g·batch + pass); the tree comes in through root_v.  The list-mapped kernels pass the list position.
 template <int NB>
 __device__ __forceinline__ void backup_pass(const SearchDev& S, const int g, const int pass, const uint32_t root_v, RootPre* pre = nullptr) {
     const size_t slot = (size_t)g * (size_t)S.batch + (size_t)pass;

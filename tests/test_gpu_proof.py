@@ -151,13 +151,15 @@ def test_selfplay_equals_a_replay_driven_by_the_reference():
     assert step1 >= 1 and excluded >= 1 and ref.stats["games_finished"] == 9 and max(ref.generation) >= 2
 
 
-def test_selfplay_with_partial_compacted_lists():
+@pytest.mark.parametrize("batch,rollouts", [(1, 48), (2, 16)])
+def test_selfplay_with_partial_compacted_lists(batch, rollouts):
     """a schedule with boost_factor 2: once a slot has been recycled the games under boost_plies are some of the live ones
-    only, so the boosted rounds run through the _list kernels"""
-    e, ref = _selfplay_against_the_reference(4, 6, 10, seed=3, boost_plies=6, boost_factor=2)
+    only, so the boosted rounds run through the list-mapped kernels; batch 2: through k_backup_select_batch<.., LIST, PROOF>, the
+    one instantiation of the tree kernels that no other test reaches"""
+    e, ref = _selfplay_against_the_reference(4, 6, 10, seed=3, rollouts=rollouts, batch=batch, boost_plies=6, boost_factor=2)
     sched = e.selfplay_schedule_stats()
     print(sched, ref.partial_lists, ref.counters())
-    assert ref.partial_lists > 0 and sched["compact_iterations"] == ref.partial_lists * 48
+    assert ref.partial_lists > 0 and sched["compact_iterations"] == ref.partial_lists * rollouts
     assert ref.counters()["nodes_proven"] > 0
 
 
@@ -165,7 +167,7 @@ def test_selfplay_with_partial_compacted_lists():
 def test_selfplay_explores_with_candidates_left_out(n, games, rollouts, seed):
     """exploit_plies beyond every game: each pick is the draw, so the children decided for the opponent are left out INSIDE the
     draw (their visits taken as 0).  Every ply is boosted and a finished slot retires, so from the first finished game on the
-    boosted rounds run over a partial list: the _list kernels compiled for 5 and 6.  The seeds are ones for which the reference
+    boosted rounds run over a partial list: the list-mapped kernels compiled for 5 and 6.  The seeds are ones for which the reference
     alone makes such picks"""
     e, ref = _selfplay_against_the_reference(n, games, games, seed, rollouts=rollouts, exploit_plies=10000, boost_plies=512, boost_factor=2)
     masked = [p for p in ref.picks if p[5] > 0 and p[4] == 2 and not p[6]]
