@@ -482,8 +482,21 @@ TG_API int tg_search_pool(TgEngine* e, uint64_t* nodes_total, uint64_t* nodes_in
  *   largest |value| (the longest defence); 0 when value is 0.
  * The levels L = 1, 2, ... are deepened in turn, one launch each.  Without TG_SOLVE_ALL_MOVES a position stops at the first
  * level that decides it (some move wins, or all moves lose): move values that need more plies stay 0.  With it every level
- * up to `depth` runs and the move table is complete.  "Forced win" means by road OR by flats, not a road-only tinue.
- * A finished position, an inactive or a dead game gives counts 0, value 0, best 0.
+ * up to `depth` runs and the move table is complete.  A finished position, an inactive or a dead game gives counts 0,
+ * value 0, best 0.
+ *
+ * "Wins" means by road OR by flats.  TG_SOLVE_ROAD_ONLY asks for the road-only proof instead, the tinue of Tak players (what
+ * PTN's marks ' and " stand for).  With it the definitions change in one point, the meaning of "wins":
+ *   W(s, L): some a has result(s_a) = a ROAD of m, or has s_a ongoing and X(s_a, L-1).
+ *   X(s, L): EVERY a has result(s_a) = a ROAD of the opponent, or has s_a ongoing and W(s_a, L-1).
+ *   A move that ends the game in any other way (flats for either colour, a draw of either kind) proves nothing for either
+ *   side: it gets move value 0 and ends an X test as a draw does.  A move that completes both roads is the mover's road
+ *   (Game::result gives it to the mover).
+ * Move values, value, best, the early stop, TG_SOLVE_ALL_MOVES, node_budget and budget_hit are defined on these two predicates
+ * exactly as above.  A road-only proof is also a proof by the definitions above, of the same sign and at most as long; the
+ * converse does not hold.
+ * flags: TG_SOLVE_ALL_MOVES (bit 0) | TG_SOLVE_ROAD_ONLY (bit 2).  Bit 1 is not assigned: it is an unknown bit like every
+ * higher one and is rejected.
  *
  * node_budget: positions one work item = (position, root move, level) may create before it gives up that level; the move
  *   stays unproven at that level and may be proven at a later one.  budget_hit[i] = 1 if any item of position i gave up.
@@ -495,7 +508,7 @@ TG_API int tg_search_pool(TgEngine* e, uint64_t* nodes_total, uint64_t* nodes_in
  *   largest power of two that keeps the longest level launch at depth 5 on its two inputs of 4096 positions under
  *   100 ms — 69 ms (mid-game) and 45 ms (near the end) at 2^10, 156 ms and 86 ms at 2^11.  At the default most unproven
  *   depth-5 positions report budget_hit; a caller who can wait passes a larger budget (2^22 gave up nowhere on those
- *   inputs: 3.3 to 4.1 s per 4096 positions).
+ *   inputs: 3.3 to 4.1 s per 4096 positions).  The default was tuned on the default mode and holds for road-only proofs too.
  *
  * moves / move_values: n x TG_MAX_MOVES, zero past counts[i]; every other output: n.  Any output pointer may be NULL.
  * tg_solve validates the states on the host as tg_search_reset does; it needs no network and no search object.
@@ -506,10 +519,11 @@ TG_API int tg_search_pool(TgEngine* e, uint64_t* nodes_total, uint64_t* nodes_in
  * ------------------------------------------------------------------------------------- */
 #define TG_SOLVE_MAX_DEPTH 6
 #define TG_SOLVE_ALL_MOVES 1u
+#define TG_SOLVE_ROAD_ONLY 4u  /* (4, not 2: bit 1 stays unassigned and rejected) */
 #define TG_SOLVE_DEFAULT_BUDGET (1 << 10)
 typedef struct TgSolveConfig {
     int32_t depth;         /* 1 .. TG_SOLVE_MAX_DEPTH */
-    uint32_t flags;        /* TG_SOLVE_ALL_MOVES */
+    uint32_t flags;        /* TG_SOLVE_ALL_MOVES | TG_SOLVE_ROAD_ONLY */
     uint64_t node_budget;  /* positions a single (position, root move, level) work item may create before it gives up; 0 = default */
     int32_t reserved[4];   /* must be 0 */
 } TgSolveConfig;

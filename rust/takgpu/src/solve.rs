@@ -8,6 +8,8 @@ use crate::{check, net::GpuNet, pack, sys};
 
 /// `TG_SOLVE_ALL_MOVES` (an unsigned literal in the header, which the generated constants leave out)
 pub const SOLVE_ALL_MOVES: u32 = 1;
+/// `TG_SOLVE_ROAD_ONLY`: only roads win (the tinuë); a move that ends the game any other way proves nothing.  Bit 1 is not assigned.
+pub const SOLVE_ROAD_ONLY: u32 = 4;
 
 /// What the solver proved about one position.
 #[derive(Clone, Debug)]
@@ -24,8 +26,12 @@ pub struct Solved {
     pub nodes: u64,
 }
 
-fn config(depth: i32, all_moves: bool, node_budget: u64) -> sys::TgSolveConfig {
-    sys::TgSolveConfig { depth, flags: if all_moves { SOLVE_ALL_MOVES } else { 0 }, node_budget, reserved: [0; 4] }
+fn config(depth: i32, flags: u32, node_budget: u64) -> sys::TgSolveConfig {
+    sys::TgSolveConfig { depth: depth, flags: flags, node_budget: node_budget, reserved: [0; 4] }
+}
+
+fn all_moves_flag(all_moves: bool) -> u32 {
+    if all_moves { SOLVE_ALL_MOVES } else { 0 }
 }
 
 struct Arrays {
@@ -68,6 +74,11 @@ impl<const N: usize> GpuNet<N> {
     /// tg_solve on `games`: needs no weights and no search.  `depth` 1 ..= TG_SOLVE_MAX_DEPTH; `all_moves` completes the move
     /// table instead of stopping at the level that decides a position; `node_budget` 0 = the library's default.
     pub fn solve(&self, games: &[Game<N>], depth: i32, all_moves: bool, node_budget: u64) -> Result<Vec<Solved>, crate::TgError> {
+        self.solve_flags(games, depth, all_moves_flag(all_moves), node_budget)
+    }
+
+    /// `solve` with TgSolveConfig.flags spelled out: `SOLVE_ALL_MOVES | SOLVE_ROAD_ONLY` (road-only proofs, the tinuë)
+    pub fn solve_flags(&self, games: &[Game<N>], depth: i32, flags: u32, node_budget: u64) -> Result<Vec<Solved>, crate::TgError> {
         if games.is_empty() {
             return Ok(Vec::new());
         }
@@ -76,7 +87,7 @@ impl<const N: usize> GpuNet<N> {
         for (g, chunk) in games.iter().zip(states.chunks_mut(sb)) {
             pack::pack_game(g, chunk);
         }
-        let cfg = config(depth, all_moves, node_budget);
+        let cfg = config(depth, flags, node_budget);
         let mut a = Arrays::new(games.len());
         check(unsafe {
             sys::tg_solve(self.e, games.len() as i32, states.as_ptr() as *const _, &cfg, a.value.as_mut_ptr(), a.best.as_mut_ptr(),
@@ -90,8 +101,14 @@ impl<const N: usize> GpuNet<N> {
     /// the device; games outside `active` and dead games come back with no moves.  The trees are not touched.
     pub fn search_solve(&self, games: usize, active: Option<&[u8]>, depth: i32, all_moves: bool, node_budget: u64)
                         -> Result<Vec<Solved>, crate::TgError> {
+        self.search_solve_flags(games, active, depth, all_moves_flag(all_moves), node_budget)
+    }
+
+    /// `search_solve` with TgSolveConfig.flags spelled out (`SOLVE_ALL_MOVES | SOLVE_ROAD_ONLY`)
+    pub fn search_solve_flags(&self, games: usize, active: Option<&[u8]>, depth: i32, flags: u32, node_budget: u64)
+                              -> Result<Vec<Solved>, crate::TgError> {
         assert!(active.map_or(true, |m| m.len() == games), "one mask byte per game");
-        let cfg = config(depth, all_moves, node_budget);
+        let cfg = config(depth, flags, node_budget);
         let mut a = Arrays::new(games);
         check(unsafe {
             sys::tg_search_solve(self.e, &cfg, active.map_or(std::ptr::null(), <[u8]>::as_ptr), a.value.as_mut_ptr(), a.best.as_mut_ptr(),

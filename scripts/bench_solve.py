@@ -13,6 +13,13 @@ The budget ladder: the level-5 step for node_budget = 2^6 … 2^20 (every power 
 stays under 100 ms on both.  Whatever a wall-clock guard (--seconds) cuts off is listed under "not_measured".
 
     python scripts/bench_solve.py [--positions 4096] [--seconds 420] [--out profiles/r18_b_solve.json]
+
+--road-only times TG_SOLVE_ROAD_ONLY beside the default mode instead: the same two inputs, depths 3 and 5 with the early stop, at
+a budget that never gives up (2^22) and at the library's default, the arms of --arms (road, default) alternating in one job, two runs
+per arm.  No ladder: the default budget was tuned on the default mode and is kept.  With TAKGPU_LIB pointing at a build of another
+commit and --arms default the same job times that build's default mode.
+
+    python scripts/bench_solve.py --road-only [--arms road,default] [--out profiles/r24_b_tinue.json]
 """
 import argparse
 import ctypes as C
@@ -58,8 +65,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--positions", type=int, default=4096)
     ap.add_argument("--seconds", type=float, default=420.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r18_b_solve.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/r18_b_solve.json, with --road-only profiles/r24_b_tinue.json")
+    ap.add_argument("--road-only", action="store_true", help="time TG_SOLVE_ROAD_ONLY against the default mode (no budget ladder)")
+    ap.add_argument("--arms", default="road,default", help="with --road-only: the arms to time, alternating")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r24_b_tinue.json" if args.road_only else "r18_b_solve.json")
     t0 = time.time()
     e = tak_amd.Engine(5, evaluator=tak_amd.EVAL_HASH, max_batch=args.positions, policy_head=tak_amd.HEAD_FC5)
     ev = Events(e)
@@ -73,8 +84,9 @@ def main():
     doc["board_pass"] = {"ms_per_pass": ms, "positions_per_s": args.positions / ms * 1e3}
     print(f"board pass: {ms:.4f} ms per {args.positions} positions = {doc['board_pass']['positions_per_s']:.3e} positions/s", flush=True)
 
-    def run(name, depth, all_moves, budget):
-        ms, r = ev.time_ms(lambda: e.solve(sets[name], depth, all_moves=all_moves, node_budget=budget))
+    def run(name, depth, all_moves, budget, road_only=False):
+        road = {"road_only": True} if road_only else {}
+        ms, r = ev.time_ms(lambda: e.solve(sets[name], depth, all_moves=all_moves, node_budget=budget, **road))
         nodes = int(r["nodes"].sum())
         return {"input": name, "depth": depth, "all_moves": all_moves, "node_budget": budget, "ms": ms,
                 "positions_per_s": args.positions / ms * 1e3, "nodes": nodes, "nodes_per_s": nodes / ms * 1e3,
@@ -83,6 +95,31 @@ def main():
 
     big = 1 << 22
     e.solve(mid[:64], 3)  # warm-up: code objects loaded, scratch allocated
+    if args.road_only:
+        arms = [a for a in args.arms.split(",") if a]
+        assert arms and set(arms) <= {"road", "default"}, "--arms takes road and default"
+        doc.update(library="TAKGPU_LIB" if os.environ.get("TAKGPU_LIB") else "this tree", arms=arms)
+        del doc["ladder"]
+        if "road" in arms:
+            e.solve(mid[:64], 3, road_only=True)
+        for name in sets:
+            for depth in (3, 5):
+                for budget in (big, 0):
+                    for rep in range(2):
+                        for arm in arms:
+                            if time.time() - t0 > args.seconds:
+                                doc["not_measured"].append(f"run {name} depth {depth} node_budget {budget} arm {arm} rep {rep}")
+                                continue
+                            row = dict(run(name, depth, False, budget, arm == "road"), arm=arm, rep=rep)
+                            doc["runs"].append(row)
+                            print(json.dumps(row), flush=True)
+        doc["seconds"] = time.time() - t0
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+        print(f"wrote {args.out}", flush=True)
+        e.close()
+        return
     for name in sets:
         for all_moves in (False, True):
             for depth in (1, 3, 5):

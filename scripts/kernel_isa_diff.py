@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Did a change move any kernel?  Compare the device code of two source trees, kernel by kernel.
 
-    python scripts/kernel_isa_diff.py A B [--only tower_kernels.hip ...] [--jobs 8] [--show 20] [--pairs FILE]
+    python scripts/kernel_isa_diff.py A B [--only tower_kernels.hip ...] [--jobs 8] [--show 20] [--pairs FILE] [--mask-pcrel]
 
 A and B are directories that hold tak_amd/csrc/, or git revisions of this repository (exported with `git archive` into a
 temporary directory; `.` and paths are taken as directories first).  Every tak_amd/csrc/*.hip of each tree is compiled
@@ -14,7 +14,9 @@ files is `twice`, a failure of its own.  A kernel that was renamed is paired thr
 names): its line shows `OLD → NEW`.  What llvm-objdump prints behind a symbol's last instruction — the zero fill up to the next
 symbol's alignment (`...`), the s_nop / s_code_end padding behind the last symbol of .text — is dropped: it belongs to the symbol's
 place in its file, not to the kernel, and differs as soon as a kernel has another neighbour.  --only is applied per tree to the
-files that exist there.  Per symbol one line: same / differs / only in A / only in B / twice; then a summary line.  Exit status 0
+files that exist there.  --mask-pcrel replaces the literal of the `s_add_u32` that follows an `s_getpc_b64` (the pc-relative distance to a
+constant table in .rodata) by `<pcrel>`: it changes whenever a file gains or loses code between the table and the kernel, which is the
+kernel's place in its file again, and with the mask such a kernel is `same`.  Per symbol one line: same / differs / only in A / only in B / twice; then a summary line.  Exit status 0
 only if every symbol is `same`.  Needs hipcc and no GPU.
 """
 import argparse
@@ -63,7 +65,7 @@ def compile_device(csrc, name, outdir, flags):
     return obj
 
 
-def disassembly(obj):
+def disassembly(obj, mask_pcrel=False):
     """symbol → its instructions as text: no addresses, no encodings."""
     out = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", "--no-leading-addr", obj], check=True,
                          stdout=subprocess.PIPE, text=True).stdout
@@ -75,6 +77,8 @@ def disassembly(obj):
             continue
         line = line.split("//")[0].strip()  # the trailing comment holds address and encoding
         if cur is not None and line:
+            if mask_pcrel and cur and cur[-1].startswith("s_getpc_b64"):
+                line = re.sub(r"^(s_add_u32 s\d+, s\d+, )0x[0-9a-f]+$", r"\1<pcrel>", line)
             cur.append(line)
     # what the assembler puts behind a symbol's last instruction belongs to its place in the file, not to it: the zero fill up to
     # the next symbol's alignment (`...`) and the s_nop / s_code_end padding behind the last symbol of the section
@@ -109,7 +113,7 @@ def descriptors(obj):
     return {k.pop(".name"): k for k in kernels if ".name" in k}
 
 
-def build_tree(tree, outdir, only, jobs):
+def build_tree(tree, outdir, only, jobs, mask_pcrel=False):
     csrc = os.path.join(tree, "tak_amd", "csrc")
     names = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and (not only or f in only))
     flags = makefile_flags(csrc)
@@ -119,7 +123,7 @@ def build_tree(tree, outdir, only, jobs):
     syms, twice = {}, {}  # symbol → (file, instructions, descriptor or None); symbol → every file that emits it
     for n, o in zip(names, objs):
         desc = descriptors(o)
-        for sym, text in disassembly(o).items():
+        for sym, text in disassembly(o, mask_pcrel).items():
             if sym in syms:
                 twice.setdefault(sym, [syms[sym][0]]).append(n)
             else:
@@ -137,10 +141,11 @@ def main():
     ap.add_argument("--quiet", action="store_true", help="print only the symbols that are not `same`, and the summary")
     ap.add_argument("--pairs", help="a file of lines `OLD NEW` (mangled names; `#` starts a comment): symbol OLD of A is compared with "
                                     "symbol NEW of B, for kernels that were renamed")
+    ap.add_argument("--mask-pcrel", action="store_true", help="compare pc-relative literals (s_getpc_b64 + s_add_u32) as equal")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="kernel_isa_diff_") as tmp:
-        files_a, A, twice_a = build_tree(resolve_tree(args.a, tmp), os.path.join(tmp, "obj_a"), args.only, args.jobs)
-        files_b, B, twice_b = build_tree(resolve_tree(args.b, tmp), os.path.join(tmp, "obj_b"), args.only, args.jobs)
+        files_a, A, twice_a = build_tree(resolve_tree(args.a, tmp), os.path.join(tmp, "obj_a"), args.only, args.jobs, args.mask_pcrel)
+        files_b, B, twice_b = build_tree(resolve_tree(args.b, tmp), os.path.join(tmp, "obj_b"), args.only, args.jobs, args.mask_pcrel)
     was = {}  # NEW → OLD for the pairs that were applied: from here on A holds OLD's code under NEW's name
     for line in open(args.pairs) if args.pairs else ():
         pair = line.split("#")[0].split()

@@ -179,29 +179,36 @@ class Analysis:
             elif np.float32(info.visits) > np.float32(np.float32(top) * CANDIDATE_MOVE_RATIO):
                 self.branches.append((ply, info))
 
-    def annotate_tactics(self, solver, state, played_move, depth, node_budget=1 << 16):
+    def annotate_tactics(self, solver, state, played_move, depth, node_budget=1 << 16, road_only=False):
         """Opt-in tactical annotation of the move just recorded (call after update / add_move): `solver` (an Engine) solves
         the position after `played_move` from `state` at `depth` plies (Engine.solve).
           the opponent is proven lost      → `"` after the move, before any ?/! mark, and the comment {forced win in k}
           the move itself is proven losing → the comment {loses in k}
           otherwise, from ply 2 on (the first two plies place the opponent's stone), `'` (Tak) when the mover would win at
           once if it were their turn again: a depth-1 solve of the same position with the header's to_move byte flipped.
-        k counts the plies after the move.  `"` here means a forced win by road OR by flats within `depth` plies — not a
-        road-only tinuë, which PTN's mark strictly stands for.  node_budget: Engine.solve's (one position: see player.TACTICS_BUDGET);
-        a proof the budget cuts off is a missing mark, never a wrong one."""
+        k counts the plies after the move.  With road_only = False a win is one by road OR by flats within `depth` plies, so `"` is
+        wider than PTN's mark.  road_only = True gives PTN's own marks: every solve is a road-only proof (Engine.solve's road_only),
+        `"` stands for a tinuë, a road that cannot be stopped, with the comments {tinue in k} and {road loss in k}, each followed by
+        the proof's principal line (forced_line) as a comment of its own, and `'` for a road threat.
+        node_budget: Engine.solve's (one position: see player.TACTICS_BUDGET); a proof the budget cuts off is a missing mark, never a
+        wrong one."""
         k = len(self.played_moves) - 1
         if k < 0 or self.played_moves[k] != int(played_move) or self.move_info[k] is None:
             return
+        road = {"road_only": True} if road_only else {}  # (the default mode's calls are what they were)
         after, _ = solver.play(np.ascontiguousarray(state, np.uint8).reshape(1, -1), np.array([played_move], np.uint16))
-        value = int(solver.solve(after, int(depth), node_budget=int(node_budget))["value"][0])
+        value = int(solver.solve(after, int(depth), node_budget=int(node_budget), **road)["value"][0])
+        line = ""
+        if value != 0 and road_only:
+            line = " {" + " ".join(format_move(self.n, m) for m in forced_line(solver, after, abs(value), True, node_budget)) + "}"
         if value < 0:
-            self.tactics[k] = ('"', f" {{forced win in {-value}}}")
+            self.tactics[k] = ('"', (f" {{tinue in {-value}}}" if road_only else f" {{forced win in {-value}}}") + line)
         elif value > 0:
-            self.tactics[k] = ("", f" {{loses in {value}}}")
+            self.tactics[k] = ("", (f" {{road loss in {value}}}" if road_only else f" {{loses in {value}}}") + line)
         elif self.start_ply + k >= 2:
             again = np.array(after, np.uint8, copy=True)
             again[0, again.shape[1] - 16 + 1] ^= 1  # TgHeader.to_move
-            if int(solver.solve(again, 1, node_budget=int(node_budget))["value"][0]) > 0:
+            if int(solver.solve(again, 1, node_budget=int(node_budget), **road)["value"][0]) > 0:
                 self.tactics[k] = ("'", "")
 
     def without_branches(self):
@@ -259,6 +266,30 @@ class Analysis:
         for bply, info in self.branches:
             out.append("\n" + _format_branch(bply, info))
         return "".join(out)
+
+
+def forced_line(engine, state, depth, road_only=False, node_budget=1 << 16):
+    """The principal line of a position proven at `depth` plies (Engine.solve): the moves until the game ends, [] when nothing is
+    proven.  Both sides play the solver's `best`: the side with the proof its fastest win, the other side its longest defence;
+    after each move the new position is solved again at the plies that remain, so the line has exactly |value| moves and its
+    last move ends the game in favour of the side with the proof (with road_only by a road).  `engine` needs solve and play.
+    Raises RuntimeError if a step comes back unproven with budget_hit set: the budget, not the position, cut the line."""
+    road = {"road_only": True} if road_only else {}
+    cur = np.ascontiguousarray(state, np.uint8).reshape(1, -1)
+    line, left = [], int(depth)
+    while left > 0:
+        r = engine.solve(cur, left, node_budget=int(node_budget), **road)
+        value = int(r["value"][0])
+        if value == 0:
+            if "budget_hit" in r and int(r["budget_hit"][0]):
+                raise RuntimeError(f"forced_line: node_budget {node_budget} ran out {len(line)} moves into the line")
+            if line:
+                raise RuntimeError(f"forced_line: the proof does not continue {len(line)} moves into the line")
+            break
+        line.append(int(r["best"][0]))
+        cur, _ = engine.play(cur, np.array([line[-1]], np.uint16))
+        left = abs(value) - 1
+    return line
 
 
 def root_eval(engine, states, ensemble=True):

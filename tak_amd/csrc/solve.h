@@ -25,14 +25,18 @@ struct SolveDev {
     unsigned long long* nodes;
     // per item
     unsigned long long* item_nodes;  // positions created by ws_play, all levels
-    uint8_t* item_flag;      // ITEM_DRAWN | ITEM_GAVE_UP
+    uint8_t* item_flag;      // ITEM_ENDED | ITEM_GAVE_UP
 };
-enum : uint8_t { ITEM_DRAWN = 1, ITEM_GAVE_UP = 2 };  // the root move ends the game in a draw (nothing left to prove); a level ran out of budget
+// ITEM_ENDED: the root move ends the game and proves nothing for either side, so nothing is left to prove (a draw; under
+// TG_SOLVE_ROAD_ONLY also flats of either colour).  ITEM_GAVE_UP: a level ran out of budget.
+enum : uint8_t { ITEM_ENDED = 1, ITEM_GAVE_UP = 2 };
 
 void launch_solve_root(hipStream_t st, const SolveDev& D);
 void launch_solve_scan(hipStream_t st, const SolveDev& D);
-// level L = 1 … TG_SOLVE_MAX_DEPTH over `items` work items, then the fold of every position
-void launch_solve_level(hipStream_t st, const SolveDev& D, int level, int items);
+// level L = 1 … TG_SOLVE_MAX_DEPTH over `items` work items, then the fold of every position.  `road` (TG_SOLVE_ROAD_ONLY) picks
+// the ROAD instantiation: a template argument and not a field of SolveDev, which no kernel would read and which would move the
+// kernel arguments of the default mode.
+void launch_solve_level(hipStream_t st, const SolveDev& D, bool road, int level, int items);
 void launch_solve_fold(hipStream_t st, const SolveDev& D);
 
 }  // namespace tg

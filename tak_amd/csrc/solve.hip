@@ -21,7 +21,7 @@ static int check_config(const TgSolveConfig* cfg, const char* who, uint32_t* bud
     const std::string w(who);
     if (!cfg) return fail(TG_ERR_INVALID_ARG, w + ": null cfg");
     if (cfg->depth < 1 || cfg->depth > TG_SOLVE_MAX_DEPTH) return fail(TG_ERR_INVALID_ARG, w + ": depth must be 1 .. TG_SOLVE_MAX_DEPTH (6)");
-    if (cfg->flags & ~TG_SOLVE_ALL_MOVES) return fail(TG_ERR_INVALID_ARG, w + ": unknown bits in flags");
+    if (cfg->flags & ~(TG_SOLVE_ALL_MOVES | TG_SOLVE_ROAD_ONLY)) return fail(TG_ERR_INVALID_ARG, w + ": unknown bits in flags");
     for (int i = 0; i < 4; i++)
         if (cfg->reserved[i]) return fail(TG_ERR_INVALID_ARG, w + ": reserved must be 0");
     const uint64_t b = cfg->node_budget ? cfg->node_budget : (uint64_t)TG_SOLVE_DEFAULT_BUDGET;
@@ -44,6 +44,7 @@ static int solve_chunk(TgEngine* e, int K, const uint8_t* d_states, const uint8_
                        const TgSolveConfig& cfg, uint32_t budget, const SolveOut& o, size_t row0, const char* who) {
     Solver* s = e->solver;
     const size_t k = (size_t)K, R = k * TG_MAX_MOVES;
+    const bool road = (cfg.flags & TG_SOLVE_ROAD_ONLY) != 0;
     SolveDev D{};
     D.states = d_states;
     D.active = d_active;
@@ -76,7 +77,7 @@ static int solve_chunk(TgEngine* e, int K, const uint8_t* d_states, const uint8_
         TG_HIP(hipMemsetAsync(D.item_nodes, 0, (size_t)items * sizeof *D.item_nodes, e->stream));
         TG_HIP(hipMemsetAsync(D.item_flag, 0, (size_t)items, e->stream));
         for (int level = 1; level <= cfg.depth; level++) {
-            launch_solve_level(e->stream, D, level, items);
+            launch_solve_level(e->stream, D, road, level, items);
             launch_solve_fold(e->stream, D);
         }
         TG_HIP(hipGetLastError());

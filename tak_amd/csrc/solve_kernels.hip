@@ -2,7 +2,7 @@
 // Kernels behind tg_solve / tg_search_solve; the definitions they implement (W, X, move values) are in include/takgpu.h.
 //
 // Shape: k_solve_root (one wave per position: move generation, finished roots answered at once), k_solve_scan (item offsets),
-// then per level L = 1 … depth one k_solve_level<L> (one wave per (position, root move)) and one k_solve_fold (one wave per
+// then per level L = 1 … depth one k_solve_level<L, ROAD> (one wave per (position, root move)) and one k_solve_fold (one wave per
 // position).  All on one stream; the only host wait is the one that sizes the item grid, before level 1.
 //
 // A work item replays its root move and asks X(s_a, L-1), then W(s_a, L-1).  Both are compile-time recursions over the
@@ -27,9 +27,11 @@ struct SolveCtx {
     bool over;         // cnt passed the budget: nothing proven from here on
 };
 
-// `r` is a win of colour `who`, by road or by flats
+// `r` is a win of colour `who`: by road or by flats, with ROAD (TG_SOLVE_ROAD_ONLY) by road alone
+template <bool ROAD>
 __device__ __forceinline__ bool won_by(uint32_t r, uint32_t who) {
-    return who == 0 ? (r == TG_WHITE_ROAD || r == TG_WHITE_FLAT) : (r == TG_BLACK_ROAD || r == TG_BLACK_FLAT);
+    if constexpr (ROAD) return who == 0 ? r == TG_WHITE_ROAD : r == TG_BLACK_ROAD;
+    else return who == 0 ? (r == TG_WHITE_ROAD || r == TG_WHITE_FLAT) : (r == TG_BLACK_ROAD || r == TG_BLACK_FLAT);
 }
 
 __device__ __forceinline__ int list_moves(const WState& s, const Geom& g, uint16_t* mv) {
@@ -38,11 +40,11 @@ __device__ __forceinline__ int list_moves(const WState& s, const Geom& g, uint16
     return c < TG_MAX_MOVES ? c : TG_MAX_MOVES;
 }
 
-template <int L>
+template <int L, bool ROAD>
 __device__ __forceinline__ bool x_test(const WState& s, const Geom& g, SolveCtx& c);
 
 // W(s, L): some move wins at once, or leads to a position whose mover loses within L-1.  L = 1 is the instant-win scan.
-template <int L>
+template <int L, bool ROAD>
 __device__ __forceinline__ bool w_test(const WState& s, const Geom& g, SolveCtx& c) {
     uint16_t* mv = c.lds + (L - 1) * TG_MAX_MOVES;
     const int count = list_moves(s, g, mv);
@@ -51,10 +53,10 @@ __device__ __forceinline__ bool w_test(const WState& s, const Geom& g, SolveCtx&
         ws_play(t, uni((uint32_t)mv[k]), g);
         if (++c.cnt > c.budget) { c.over = true; return false; }
         const uint32_t r = ws_result(t, g);
-        if (won_by(r, s.to_move)) return true;
+        if (won_by<ROAD>(r, s.to_move)) return true;
         if constexpr (L > 1) {
             if (r == TG_ONGOING) {
-                if (x_test<L - 1>(t, g, c)) return true;
+                if (x_test<L - 1, ROAD>(t, g, c)) return true;
                 if (c.over) return false;
             }
         }
@@ -63,8 +65,8 @@ __device__ __forceinline__ bool w_test(const WState& s, const Geom& g, SolveCtx&
 }
 
 // X(s, L): every move loses at once, or leads to a position whose mover wins within L-1.  The first move that does neither
-// (a draw among them) ends the test; so does a sub-test that ran out of budget, which comes back as "not proven".
-template <int L>
+// (a draw among them, with ROAD a flat ending too) ends the test; so does a sub-test that ran out of budget, which comes back as "not proven".
+template <int L, bool ROAD>
 __device__ __forceinline__ bool x_test(const WState& s, const Geom& g, SolveCtx& c) {
     uint16_t* mv = c.lds + (L - 1) * TG_MAX_MOVES;
     const int count = list_moves(s, g, mv);
@@ -73,9 +75,9 @@ __device__ __forceinline__ bool x_test(const WState& s, const Geom& g, SolveCtx&
         ws_play(t, uni((uint32_t)mv[k]), g);
         if (++c.cnt > c.budget) { c.over = true; return false; }
         const uint32_t r = ws_result(t, g);
-        if (won_by(r, s.to_move ^ 1u)) continue;
+        if (won_by<ROAD>(r, s.to_move ^ 1u)) continue;
         if constexpr (L > 1) {
-            if (r == TG_ONGOING && w_test<L - 1>(t, g, c)) continue;
+            if (r == TG_ONGOING && w_test<L - 1, ROAD>(t, g, c)) continue;
         }
         return false;
     }
@@ -127,7 +129,7 @@ __global__ __launch_bounds__(256) void k_solve_scan(SolveDev D) {
     for (int i = i0; i < i1; i++) { D.offsets[i] = acc; acc += items(i); }
 }
 
-template <int L>
+template <int L, bool ROAD>
 __global__ __launch_bounds__(64) void k_solve_level(SolveDev D, int n_items) {
     __shared__ uint16_t lds[(L > 1 ? L - 1 : 1) * TG_MAX_MOVES];
     const int item = (int)blockIdx.x;
@@ -143,7 +145,7 @@ __global__ __launch_bounds__(64) void k_solve_level(SolveDev D, int n_items) {
     const size_t slot = (size_t)pos * TG_MAX_MOVES + (size_t)k;
     if (D.move_values[slot] != 0) return;             // proven at an earlier level
     if (!D.all_moves && D.decided[pos]) return;       // the position stopped at the level that decided it
-    if (D.item_flag[item] & ITEM_DRAWN) return;
+    if (D.item_flag[item] & ITEM_ENDED) return;
     const Geom g = make_geom(D.n);
     WState s;
     ws_load(s, D.states + (size_t)pos * g.bytes, g);
@@ -152,19 +154,19 @@ __global__ __launch_bounds__(64) void k_solve_level(SolveDev D, int n_items) {
     const uint32_t r = ws_result(t, g);
     SolveCtx c{lds, D.budget, 1u, false};
     int v = 0;
-    bool drawn = false;
+    bool ended = false;  // the root move ends the game and proves nothing: a draw, with ROAD also flats of either colour
     if constexpr (L == 1) {
-        if (won_by(r, s.to_move)) v = 1;
-        else if (won_by(r, s.to_move ^ 1u)) v = -1;
-        else drawn = r != TG_ONGOING;
+        if (won_by<ROAD>(r, s.to_move)) v = 1;
+        else if (won_by<ROAD>(r, s.to_move ^ 1u)) v = -1;
+        else ended = r != TG_ONGOING;
     } else {  // (an item that reaches a later level has an ongoing s_a)
-        if (x_test<L - 1>(t, g, c)) v = L;
-        else if (!c.over && w_test<L - 1>(t, g, c)) v = -L;
+        if (x_test<L - 1, ROAD>(t, g, c)) v = L;
+        else if (!c.over && w_test<L - 1, ROAD>(t, g, c)) v = -L;
     }
     if (lane_id() == 0) {
         if (v) D.move_values[slot] = (int8_t)v;
         D.item_nodes[item] += (unsigned long long)c.cnt;
-        if (drawn || c.over) D.item_flag[item] = (uint8_t)(D.item_flag[item] | (drawn ? ITEM_DRAWN : 0) | (c.over ? ITEM_GAVE_UP : 0));
+        if (ended || c.over) D.item_flag[item] = (uint8_t)(D.item_flag[item] | (ended ? ITEM_ENDED : 0) | (c.over ? ITEM_GAVE_UP : 0));
     }
 }
 
@@ -232,9 +234,13 @@ void launch_solve_root(hipStream_t st, const SolveDev& D) {
 void launch_solve_scan(hipStream_t st, const SolveDev& D) {
     if (D.K > 0) hipLaunchKernelGGL(k_solve_scan, dim3(1), dim3(256), 0, st, D);
 }
-void launch_solve_level(hipStream_t st, const SolveDev& D, int level, int items) {
+void launch_solve_level(hipStream_t st, const SolveDev& D, bool road, int level, int items) {
     if (items <= 0) return;
-#define TG_SOLVE_LEVEL(L) case L: hipLaunchKernelGGL(k_solve_level<L>, dim3(items), dim3(64), 0, st, D, items); break
+#define TG_SOLVE_LEVEL(L)                                                                                      \
+    case L:                                                                                                    \
+        if (road) hipLaunchKernelGGL((k_solve_level<L, true>), dim3(items), dim3(64), 0, st, D, items);        \
+        else hipLaunchKernelGGL((k_solve_level<L, false>), dim3(items), dim3(64), 0, st, D, items);            \
+        break
     switch (level) {
         TG_SOLVE_LEVEL(1);
         TG_SOLVE_LEVEL(2);

@@ -668,22 +668,28 @@ class Engine:
                     moves=np.zeros((k, TG_MAX_MOVES), np.uint16), move_values=np.zeros((k, TG_MAX_MOVES), np.int8),
                     budget_hit=np.zeros(k, np.uint8), nodes=np.zeros(k, np.uint64))
 
-    def solve(self, states, depth, all_moves=False, node_budget=0, flags=None):
+    @staticmethod
+    def _solve_flags(all_moves, road_only):
+        return (TG_SOLVE_ALL_MOVES if all_moves else 0) | (TG_SOLVE_ROAD_ONLY if road_only else 0)
+
+    def solve(self, states, depth, all_moves=False, node_budget=0, flags=None, road_only=False):
         """Exact forced wins within `depth` plies of every position (definitions: include/takgpu.h).  Returns a dict of arrays:
         value / best / counts / budget_hit / nodes [k], moves / move_values [k, TG_MAX_MOVES] (zero past counts).
         all_moves: deepen every position to `depth` and complete the move table instead of stopping at the deciding level;
-        node_budget: positions one (position, root move, level) may create, 0 = the library's default; flags overrides all_moves."""
+        road_only: only roads win (TG_SOLVE_ROAD_ONLY, the tinuë), a move that ends the game any other way proves nothing;
+        node_budget: positions one (position, root move, level) may create, 0 = the library's default;
+        flags overrides all_moves and road_only."""
         states, k = self._states(states)
-        cfg = TgSolveConfig(int(depth), (TG_SOLVE_ALL_MOVES if all_moves else 0) if flags is None else int(flags), int(node_budget))
+        cfg = TgSolveConfig(int(depth), self._solve_flags(all_moves, road_only) if flags is None else int(flags), int(node_budget))
         o = self._solve_out(k)
         self._check(self.lib.tg_solve(self.h, k, _p(states), C.byref(cfg), _p(o["value"]), _p(o["best"]), _p(o["counts"]), _p(o["moves"]),
                                       _p(o["move_values"]), _p(o["budget_hit"]), _p(o["nodes"])))
         return o
 
-    def search_solve(self, depth, active=None, all_moves=False, node_budget=0):
+    def search_solve(self, depth, active=None, all_moves=False, node_budget=0, road_only=False, flags=None):
         """Engine.solve on the current roots of the live search / self-play object, in place on the device; games outside
         `active` and dead games give zero rows.  The trees are not touched."""
-        cfg = TgSolveConfig(int(depth), TG_SOLVE_ALL_MOVES if all_moves else 0, int(node_budget))
+        cfg = TgSolveConfig(int(depth), self._solve_flags(all_moves, road_only) if flags is None else int(flags), int(node_budget))
         o = self._solve_out(self.games)
         self._check(self.lib.tg_search_solve(self.h, C.byref(cfg), _p(_mask(active)), _p(o["value"]), _p(o["best"]), _p(o["counts"]),
                                              _p(o["moves"]), _p(o["move_values"]), _p(o["budget_hit"]), _p(o["nodes"])))

@@ -20,16 +20,19 @@ TACTICS_BUDGET = 1 << 16
 
 class Player:
     def __init__(self, engine, batch, save_examples, game, arena_nodes=1 << 16, seed=0, create_analysis=False, symmetry=None, tactics=0,
-                 tactics_budget=TACTICS_BUDGET, proof=None):
+                 tactics_budget=TACTICS_BUDGET, proof=None, tactics_road_only=False):
         """Player::new(network, batch, save_examples, create_analysis, &game); `game` is a packed state.
         symmetry: "hashed" / SYMM_HASHED = every evaluated leaf goes to the network as a hashed dihedral image (Engine.search_set_symmetry)
         tactics: D > 0 = the analysis annotates every played move that has info with the forced-win solver at depth D (Analysis.annotate_tactics);
         0 (default) = no solver call anywhere
         tactics_budget: node_budget of this player's solver calls (pick_move's and the annotation's)
+        tactics_road_only: this player's solver calls prove roads only (Engine.solve's road_only, the tinuë): pick_move plays a forced
+        road and avoids moves into one, the annotation writes PTN's road marks
         proof: "on" / PROOF_ON / True = proven values in the tree (Engine.search_set_proof) and the proof-aware pick_move"""
         self.e = engine
         self.tactics = int(tactics)
         self.tactics_budget = int(tactics_budget)
+        self.tactics_road_only = bool(tactics_road_only)
         self.last_tactics = None  # the Engine.search_solve result of the last pick_move(…, tactics > 0)
         self.proof = proof is not None and proof not in (0, False, "off")
         self.last_proof = None  # with proof: the Engine.search_proof result of the last pick_move
@@ -80,7 +83,8 @@ class Player:
                 raise RuntimeError("pick_move: the root's children are not the proof's status list")
             status = node_status(p["child_status"][0, : len(moves)])
         if tactics > 0:
-            r = self.last_tactics = self.e.search_solve(int(tactics), node_budget=self.tactics_budget)
+            road = {"road_only": True} if self.tactics_road_only else {}
+            r = self.last_tactics = self.e.search_solve(int(tactics), node_budget=self.tactics_budget, **road)
             if int(r["value"][0]) > 0:
                 return int(r["best"][0])
             c = int(r["counts"][0])
@@ -126,7 +130,8 @@ class Player:
             if with_info:
                 self.analysis.update(self.debug(MAX_BRANCH_LENGTH), move)
                 if self.tactics > 0:
-                    self.analysis.annotate_tactics(self.e, self.state(), move, self.tactics, node_budget=self.tactics_budget)
+                    self.analysis.annotate_tactics(self.e, self.state(), move, self.tactics, node_budget=self.tactics_budget,
+                                                   road_only=self.tactics_road_only)
             else:
                 self.analysis.add_move_without_info(move)
         self.e.search_play(np.array([move], np.uint16))
