@@ -63,6 +63,12 @@ typedef enum TgStatus {
 #define TG_LIMIT_DEPTH 256          /* longest selection path (plies below the root)                     */
 #define TG_LIMIT_VISITS (1 << 22)   /* visits + virtual visits of one node (exploration-rate table)      */
 #define TG_LIMIT_GAME_PLIES 512     /* examples staged per self-play game = plies of one game            */
+/* The move-list capacity TG_MAX_MOVES (512, below) is one of these capacities wherever a list is staged: a position INSIDE a search
+ * tree (a node the selection expands, a root the self-play driver scans for an instant win) with more legal moves is treated as the
+ * three above — the game retired in self-play, the sticky TG_ERR_LIMIT in a caller-driven search and in tg_reanalyse.  A position a
+ * caller HANDS IN with a longer list (tg_movegen, tg_solve, a frontier of tg_perft at depth >= 2) is TG_ERR_INVALID_ARG; inside the
+ * forced-win solver a longer list is a give-up (tg_solve below).  Such positions exist: on 6x6 eight stacks of six stones topped by
+ * the mover in the interior give 1076 moves, on 5x5 eight stacks of five give 531.  Ordinary play is not known to reach them. */
 
 typedef enum TgPlayError { /* per-item result of tg_play, 0 = Ok(()) */
     TG_PLAY_OK = 0,
@@ -241,7 +247,10 @@ TG_API int tg_augment_examples(TgEngine* e, int n, const void* states, const int
                         const uint32_t* visits, void* out_states, float* pi);
 
 /* perft of tak/tests/perft.rs:3-18 evaluated on the GPU: one count per input state.
- * depth ≥ 0.  Expands level by level on the device (movegen+play+result kernels). */
+ * depth ≥ 0.  Expands level by level on the device (movegen+play+result kernels).  The positions a level expands are staged
+ * in rows of TG_MAX_MOVES moves: at depth >= 2 an ongoing position with a longer list on a level that is expanded makes the call
+ * return TG_ERR_INVALID_ARG (tg_movegen's rule; the message names the root it lies below) before that level is expanded.  The
+ * last level is only counted, so depth 1 returns the true count of any position. */
 TG_API int tg_perft(TgEngine* e, int n, const void* states, int depth, uint64_t* counts);
 
 /* ---------------------------------------------------------------------------------------
@@ -503,6 +512,14 @@ TG_API int tg_search_pool(TgEngine* e, uint64_t* nodes_total, uint64_t* nodes_in
  *   With budget_hit 0 the outputs are exactly the definitions above.  With budget_hit 1 every non-zero entry is still a
  *   sound proof: the sign of the exact answer at the same depth, |d| >= the exact |d|; nothing else is promised.
  *   nodes[i] (positions created by play for position i) <= counts[i] * depth * (node_budget + TG_MAX_MOVES).
+ *   Move-list capacity inside the tree: a position BELOW a root with more than TG_MAX_MOVES moves is a give-up of the same kind.
+ *   Its list is the first TG_MAX_MOVES moves of possible_moves.  X on such a position does not hold (nothing can be said of
+ *   "every move") and no move of it is played; W on it tries those TG_MAX_MOVES moves and holds if one of them wins, else it does
+ *   not hold.  In both failing cases the item is marked as given up, and unlike the node budget the search of the item goes on:
+ *   budget_hit[i] = 1 if a test that failed on a cut list was reached at any level that ran for position i (tests are tried in
+ *   move order and stop at the first move that decides them, so a cut list behind that move is never reached).  The promise
+ *   above holds: every non-zero entry is a sound proof.  A ROOT with more than TG_MAX_MOVES moves is TG_ERR_INVALID_ARG naming
+ *   the position, returned before any level is searched.
  *   0 = TG_SOLVE_DEFAULT_BUDGET, which exists so that no launch on a shared card can run away; values above 2^31 - 1
  *   count as 2^31 - 1.  The default is 2^10, fixed by scripts/bench_solve.py on an MI355X (profiles/r18_b_solve.json): the
  *   largest power of two that keeps the longest level launch at depth 5 on its two inputs of 4096 positions under

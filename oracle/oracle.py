@@ -165,6 +165,16 @@ def movegen(n, states):
     return moves, counts
 
 
+def movegen_full(n, states, capacity=4096):
+    """movegen without the cut at TG_MAX_MOVES: (moves[k, capacity], counts).  The capacity must hold the longest list."""
+    states, k = _states(n, states)
+    moves = np.zeros((k, capacity), np.uint16)
+    counts = np.zeros(k, np.int32)
+    lib().orc_movegen_full(n, k, _p(states), int(capacity), _p(moves), _p(counts))
+    assert k == 0 or counts.max() <= capacity, f"a position has {counts.max()} moves, capacity {capacity}"
+    return moves, counts
+
+
 def result(n, states):
     states, k = _states(n, states)
     out = np.zeros(k, np.uint8)

@@ -92,6 +92,19 @@ void orc_movegen(int n, int k, const uint8_t* states, TgMove* moves, int32_t* co
     }
 }
 
+// orc_movegen with the row length given by the caller: moves[i * capacity + j] for j < min(counts[i], capacity).  With a capacity
+// above the longest list this is the whole list of possible_moves, which orc_movegen cuts at TG_MAX_MOVES.
+void orc_movegen_full(int n, int k, const uint8_t* states, int capacity, TgMove* moves, int32_t* counts) {
+    size_t sb = state_bytes(n);
+    for (int i = 0; i < k; i++) {
+        std::vector<Move> mv;
+        Game g = unpack(states + i * sb, n);
+        g.possible_moves(mv);
+        counts[i] = (int32_t)mv.size();
+        for (size_t j = 0; j < mv.size() && j < (size_t)capacity; j++) moves[(size_t)i * capacity + j] = encode_move(mv[j], n);
+    }
+}
+
 void orc_result(int n, int k, const uint8_t* states, uint8_t* results) {
     size_t sb = state_bytes(n);
 #pragma omp parallel for schedule(static) if (k >= 4096)

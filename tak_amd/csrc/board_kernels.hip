@@ -95,6 +95,7 @@ __global__ __launch_bounds__(256) void k_perft_expand(const uint8_t* __restrict_
     if (ws_result(s, g) != TG_ONGOING) return;
     uint16_t* mv = mv_lds[threadIdx.x >> 6];
     int c = ws_movegen(s, g, TG_MAX_MOVES, [&](int idx, uint32_t code) { mv[idx] = (uint16_t)code; });
+    if (c > TG_MAX_MOVES) c = TG_MAX_MOVES;  // the row holds no more (tg_perft refuses such a frontier before it launches this)
     __builtin_amdgcn_wave_barrier();
     int64_t off = offsets[gi];
     int root = root_of[gi];

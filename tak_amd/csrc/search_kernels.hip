@@ -364,7 +364,7 @@ __global__ __launch_bounds__(WPB * 64) void k_sp_instant_win(SearchDev S, SelfPl
     int count = ws_movegen(s, geo, EX_MOVES, [&](int idx, uint32_t code) { mv[idx] = (uint16_t)code; });
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (count > EX_MOVES) {  // (no such position exists on boards up to 6×6; kept as a bound on the LDS staging)
+    if (count > EX_MOVES) {  // (such positions exist on 5×5 and 6×6, takgpu.h TG_LIMIT_*: the capacity is reported, the list is never used cut)
         limit_hit(S, g, ERRF_MOVES);
         if (lane == 0) P.fin[g] = FIN_ABORTED;
         return;

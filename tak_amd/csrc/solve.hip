@@ -68,8 +68,13 @@ static int solve_chunk(TgEngine* e, int K, const uint8_t* d_states, const uint8_
     launch_solve_scan(e->stream, D);
     TG_HIP(hipGetLastError());
     int32_t items = 0;
+    std::vector<int32_t> h_counts(k);
     TG_HIP(hipMemcpyAsync(&items, D.offsets + K, sizeof items, hipMemcpyDeviceToHost, e->stream));
+    TG_HIP(hipMemcpyAsync(h_counts.data(), D.counts, k * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     TG_HIP(hipStreamSynchronize(e->stream));
+    for (size_t i = 0; i < k; i++)  // a root above the capacity is refused before anything is searched (roots inside the tree: takgpu.h)
+        if (h_counts[i] > TG_MAX_MOVES)
+            return fail(TG_ERR_INVALID_ARG, std::string(who) + ": position " + std::to_string(row0 + i) + " has more than TG_MAX_MOVES moves");
     if (items < 0 || (size_t)items > R) return fail(TG_ERR_STATE, std::string(who) + ": corrupt item count");
     if (items > 0) {
         TG_HIP(bind(s->item_nodes, D.item_nodes, (size_t)items));
@@ -89,11 +94,6 @@ static int solve_chunk(TgEngine* e, int K, const uint8_t* d_states, const uint8_
     TG_HIP(copy_out(o.move_values ? o.move_values + row0 * TG_MAX_MOVES : nullptr, D.move_values, R));
     TG_HIP(copy_out(o.budget_hit ? o.budget_hit + row0 : nullptr, D.budget_hit, k));
     TG_HIP(copy_out(o.nodes ? o.nodes + row0 : nullptr, D.nodes, k));
-    std::vector<int32_t> h_counts(k);
-    TG_HIP(copy_out(h_counts.data(), D.counts, k));
-    for (size_t i = 0; i < k; i++)
-        if (h_counts[i] > TG_MAX_MOVES)
-            return fail(TG_ERR_INVALID_ARG, std::string(who) + ": position " + std::to_string(row0 + i) + " has more than TG_MAX_MOVES moves");
     if (o.counts) std::memcpy(o.counts + row0, h_counts.data(), k * sizeof(int32_t));
     return TG_OK;
 }

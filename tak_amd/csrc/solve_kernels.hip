@@ -25,6 +25,7 @@ struct SolveCtx {
     uint32_t budget;
     uint32_t cnt;      // positions created by ws_play in this item and level
     bool over;         // cnt passed the budget: nothing proven from here on
+    bool cut;          // a test failed on a move list cut at TG_MAX_MOVES: the search goes on, the item is reported as given up
 };
 
 // `r` is a win of colour `who`: by road or by flats, with ROAD (TG_SOLVE_ROAD_ONLY) by road alone
@@ -34,20 +35,26 @@ __device__ __forceinline__ bool won_by(uint32_t r, uint32_t who) {
     else return who == 0 ? (r == TG_WHITE_ROAD || r == TG_WHITE_FLAT) : (r == TG_BLACK_ROAD || r == TG_BLACK_FLAT);
 }
 
-__device__ __forceinline__ int list_moves(const WState& s, const Geom& g, uint16_t* mv) {
+// → the moves staged (at most TG_MAX_MOVES); `cut` = the position has more than that, so the row holds only the first TG_MAX_MOVES of
+// its list (include/takgpu.h "Move-list capacity inside the tree": the caller gives up instead of deciding on the part)
+__device__ __forceinline__ int list_moves(const WState& s, const Geom& g, uint16_t* mv, bool& cut) {
     const int c = ws_movegen(s, g, TG_MAX_MOVES, [&](int idx, uint32_t code) { mv[idx] = (uint16_t)code; });
     __builtin_amdgcn_wave_barrier();  // the list is read back wave-uniformly below: lanes read what other lanes wrote
-    return c < TG_MAX_MOVES ? c : TG_MAX_MOVES;
+    cut = c > TG_MAX_MOVES;
+    return cut ? TG_MAX_MOVES : c;
 }
 
 template <int L, bool ROAD>
 __device__ __forceinline__ bool x_test(const WState& s, const Geom& g, SolveCtx& c);
 
 // W(s, L): some move wins at once, or leads to a position whose mover loses within L-1.  L = 1 is the instant-win scan.
+// A list cut at TG_MAX_MOVES is searched as far as it is staged: a win among those moves is a win; without one the test fails and
+// the item is marked as given up.
 template <int L, bool ROAD>
 __device__ __forceinline__ bool w_test(const WState& s, const Geom& g, SolveCtx& c) {
     uint16_t* mv = c.lds + (L - 1) * TG_MAX_MOVES;
-    const int count = list_moves(s, g, mv);
+    bool cut;
+    const int count = list_moves(s, g, mv, cut);
     for (int k = 0; k < count; k++) {
         WState t = s;
         ws_play(t, uni((uint32_t)mv[k]), g);
@@ -61,15 +68,20 @@ __device__ __forceinline__ bool w_test(const WState& s, const Geom& g, SolveCtx&
             }
         }
     }
+    if (cut) c.cut = true;
     return false;
 }
 
 // X(s, L): every move loses at once, or leads to a position whose mover wins within L-1.  The first move that does neither
 // (a draw among them, with ROAD a flat ending too) ends the test; so does a sub-test that ran out of budget, which comes back as "not proven".
+// "Every move" cannot be said of a list cut at TG_MAX_MOVES: such a position fails before its first move is played and the item is
+// marked as given up.
 template <int L, bool ROAD>
 __device__ __forceinline__ bool x_test(const WState& s, const Geom& g, SolveCtx& c) {
     uint16_t* mv = c.lds + (L - 1) * TG_MAX_MOVES;
-    const int count = list_moves(s, g, mv);
+    bool cut;
+    const int count = list_moves(s, g, mv, cut);
+    if (cut) { c.cut = true; return false; }
     for (int k = 0; k < count; k++) {
         WState t = s;
         ws_play(t, uni((uint32_t)mv[k]), g);
@@ -152,7 +164,7 @@ __global__ __launch_bounds__(64) void k_solve_level(SolveDev D, int n_items) {
     WState t = s;
     ws_play(t, uni((uint32_t)D.moves[slot]), g);
     const uint32_t r = ws_result(t, g);
-    SolveCtx c{lds, D.budget, 1u, false};
+    SolveCtx c{lds, D.budget, 1u, false, false};
     int v = 0;
     bool ended = false;  // the root move ends the game and proves nothing: a draw, with ROAD also flats of either colour
     if constexpr (L == 1) {
@@ -166,7 +178,8 @@ __global__ __launch_bounds__(64) void k_solve_level(SolveDev D, int n_items) {
     if (lane_id() == 0) {
         if (v) D.move_values[slot] = (int8_t)v;
         D.item_nodes[item] += (unsigned long long)c.cnt;
-        if (ended || c.over) D.item_flag[item] = (uint8_t)(D.item_flag[item] | (ended ? ITEM_ENDED : 0) | (c.over ? ITEM_GAVE_UP : 0));
+        const bool gave_up = c.over || c.cut;
+        if (ended || gave_up) D.item_flag[item] = (uint8_t)(D.item_flag[item] | (ended ? ITEM_ENDED : 0) | (gave_up ? ITEM_GAVE_UP : 0));
     }
 }
 

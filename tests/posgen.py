@@ -318,3 +318,160 @@ def covering_subset(planes, count):
     assert len(chosen) <= count, (len(chosen), count)
     chosen += [i for i in range(len(planes)) if i not in set(chosen)][: count - len(chosen)]
     return np.array(chosen)
+
+
+def from_tps(n, tps, half_komi=4, reversible_plies=0):
+    """the packed state of a TPS string ("row n/…/row 1 player move", stacks bottom → top as 1 / 2 with S or C on top); the
+    reserves are what the board leaves of the supplies"""
+    S, Cc = STONES[n]
+    board, player, number = tps.split()
+    slots = 25 if n <= 5 else 36
+    st = np.zeros(state_bytes(n), np.uint8)
+    words, meta = st[: 8 * slots].view(np.uint64), st[8 * slots: 9 * slots]
+    left = {0: [S, Cc], 1: [S, Cc]}
+    rows = board.split("/")
+    assert len(rows) == n
+    for r, text in enumerate(rows):
+        col = 0
+        for cell in text.split(","):
+            if cell[0] == "x":
+                col += int(cell[1:] or 1)
+                continue
+            top = {"S": 1, "C": 2}.get(cell[-1], 0)
+            stones = cell.rstrip("SC")
+            sq = (n - 1 - r) * n + col
+            words[sq] = sum((int(ch) - 1) << k for k, ch in enumerate(stones))
+            meta[sq] = len(stones) | (top << 6)
+            for k, ch in enumerate(stones):
+                left[int(ch) - 1][1 if top == 2 and k == len(stones) - 1 else 0] -= 1
+            col += 1
+        assert col == n, text
+    assert min(left[0] + left[1]) >= 0, "more pieces than the supplies hold"
+    to_move = int(player) - 1
+    ply = 2 * (int(number) - 1) + to_move
+    h = st[-16:]
+    h[0], h[H_TO_MOVE], h[H_PLY], h[H_PLY + 1] = n, to_move, ply & 0xFF, ply >> 8
+    h[H_WS], h[H_WC], h[H_BS], h[H_BC] = left[0][0], left[0][1], left[1][0], left[1][1]
+    h[H_KOMI], h[H_REV] = np.uint8(half_komi & 0xFF), reversible_plies
+    return st
+
+
+# ---- positions with more than TG_MAX_MOVES (512) legal moves: tests/test_long_move_lists.py, tests/test_gpu_long_move_lists.py ------
+def swap_colours(state, n):
+    """the same position with the colours exchanged (stones, reserves, the side to move; the ply moves on by one)"""
+    st = np.array(state, np.uint8, copy=True)
+    slots = 25 if n <= 5 else 36
+    words, meta = st[: 8 * slots].view(np.uint64), st[8 * slots: 9 * slots]
+    words ^= (np.uint64(1) << (meta & 63).astype(np.uint64)) - np.uint64(1)
+    h = st[-16:]
+    h[H_WS], h[H_BS], h[H_WC], h[H_BC] = h[H_BS], h[H_WS], h[H_BC], h[H_WC]
+    ply = (int(h[H_PLY]) | int(h[H_PLY + 1]) << 8) + 1
+    h[H_TO_MOVE], h[H_PLY], h[H_PLY + 1] = h[H_TO_MOVE] ^ 1, ply & 0xFF, ply >> 8
+    return st
+
+
+def symmetry_image(state, n, s):
+    """the image of a position under symmetry s of the square group: s < 4 is rotate^s, s ≥ 4 mirror (col → n − 1 − col) then
+    rotate^(s − 4), rotate being (col, row) → (row, n − 1 − col)"""
+    st = np.array(state, np.uint8, copy=True)
+    slots = 25 if n <= 5 else 36
+    words, meta = st[: 8 * slots].view(np.uint64), st[8 * slots: 9 * slots]
+    w0, m0 = words.copy(), meta.copy()
+    for sq in range(n * n):
+        col, row = sq % n, sq // n
+        if s >= 4:
+            col = n - 1 - col
+        for _ in range(s & 3):
+            col, row = row, n - 1 - col
+        words[row * n + col], meta[row * n + col] = w0[sq], m0[sq]
+    return st
+
+
+def take_back_flat(state, n, sq):
+    """the position before the side NOT to move placed the lone flat on `sq`: that flat back in its reserve, that side to move.
+    → (state, the move code of the placement: a flat on sq)"""
+    st = np.array(state, np.uint8, copy=True)
+    slots = 25 if n <= 5 else 36
+    words, meta = st[: 8 * slots].view(np.uint64), st[8 * slots: 9 * slots]
+    h = st[-16:]
+    placer = int(h[H_TO_MOVE]) ^ 1
+    assert meta[sq] == 1 and int(words[sq]) == placer, "the square does not hold a lone flat of the side that moved last"
+    words[sq], meta[sq] = 0, 0
+    h[H_BS if placer else H_WS] += 1
+    ply = (int(h[H_PLY]) | int(h[H_PLY + 1]) << 8) - 1
+    h[H_TO_MOVE], h[H_PLY], h[H_PLY + 1] = placer, ply & 0xFF, ply >> 8
+    return st, sq  # (a placement's code is square | piece << 6, and a flat is piece 0)
+
+
+def reply_table(orc, n, state, capacity=4096):
+    """per move of the position's UNCUT list, in possible_moves order: (moves, result of the child, whether the child is ongoing and
+    its mover has a move that wins at once) — by the oracle alone"""
+    state = np.ascontiguousarray(state, np.uint8).reshape(1, -1)
+    moves, counts = orc.movegen_full(n, state, capacity)
+    c = int(counts[0])
+    ch, status = orc.play(n, np.repeat(state, c, axis=0), moves[0, :c])
+    assert not status.any()
+    res = orc.result(n, ch)
+    mover = int(state[0, -16 + H_TO_MOVE]) ^ 1  # the side to move in the children
+    wins = (3, 4) if mover else (1, 2)
+    hit = np.zeros(c, bool)
+    for j in np.flatnonzero(res == 0):
+        rm, rc = orc.movegen_full(n, ch[j], capacity)
+        rch, rst = orc.play(n, np.repeat(ch[j][None], int(rc[0]), axis=0), rm[0, : rc[0]])
+        assert not rst.any()
+        hit[j] = np.isin(orc.result(n, rch), wins).any()
+    return moves[0, :c], res, hit
+
+
+LONG_LIST_TPS = {
+    # eight mover-topped stacks of height 6 in the interior: 1076 moves
+    "max": "x,x,x,x,x,x/x,x,221211,221211,x,x/x,x,221211,221211,x,x/x,x,221211,221211,x,x/x,x,221211,221211,x,x/x,x,x,x,x,x 1 51",
+    # S: 763 moves; after each of the first 512 black completes the f-file at once; the only defences (f6) lie behind index 512
+    "S": "x,x,x,x,2S,x/x,211111,111111,x,2S,2/x,212121,212121,x,2S,2/x,212121,212121,x,2S,2/x,212121,212121,x,2S,2/x,x,x,x,2S,2 1 51",
+    # white's c-file lacks only c6 (a placement early in the list): more than 512 moves, an instant road among the first 512; the
+    # black flat on a1 is the move that led here
+    "W": "x,x,x,x,x,x/x,x,221211,221211,x,x/x,x,221211,221211,x,x/x,x,221211,221211,x,x/x,x,221211,221211,x,x/2,x,1,x,x,x 1 51",
+    # exactly 512 / 513 moves (stacks of "max" trimmed until the oracle's count said so); the black flats on a1 (a2) are there to be
+    # taken back: "e512" is reached from its root by a2, "e513" by a1
+    "e512": "x,x,x,x,x,x/x,x,211,211,x,x/x,x,221211,221211,x,x/x,x,1211,211,x,x/2,x,211,1211,x,x/2,x,x,x,x,x 1 51",
+    "e513": "x,x,x,x,x,x/x,x,211,21211,x,x/x,x,1211,1211,x,x/x,x,1211,221211,x,x/x,x,211,1211,x,x/2,x,x,x,x,x 1 51",
+    "e512_bare": "x,x,x,x,x,x/x,x,21211,21211,x,x/x,x,1211,211,x,x/x,x,21211,211,x,x/x,x,211,21211,x,x/x,x,x,x,x,x 1 51",
+}
+# roots (black to move, nothing of black's on top of a square: its moves are placements only) whose children have at most 512 moves, 39
+# of them exactly 512 / at most 513, 44 of them exactly 513: the capacity's edge INSIDE the solver's tree
+EDGE_ROOT_TPS = {
+    "E512": "x,x,x,x,x,1/x,x,21211,21211,x,x/x,x,221211,1211,x,x/x,x,11,11,x,x/x,x,1211,1211,x,x/x,x,x,x,x,x 2 50",
+    "E513": "x,x,x,x,x,x/x,x,211,1211,x,x/x,x,21211,1211,x,x/x,x,1211,221211,x,x/x,x,211,1211,x,x/x,x,x,x,x,x 2 50",
+}
+
+
+def long_list_states(orc, n=6):
+    """Positions around the move-list capacity TG_MAX_MOVES = 512, built directly (they pass is_position and reserves_consistent and are
+    ongoing; whether play reaches them is beside the point: every entry point takes positions from callers).
+    → dict(states = name → packed state, roots = name → (root state, move code, name of the child the move leads to),
+           edge_roots = "E512" / "E513" → a root whose longest child list is exactly 512 / 513 (EDGE_ROOT_TPS),
+           s_images = the symmetries of S (1 … 7) whose image keeps every defence behind index 511).
+    states: "max" 1076 moves; "S" 763 moves, every one of the first 512 loses at once, the defences lie behind; "S_swapped" its colour
+    twin; "S_sym<k>" the kept images of S; "S_mirror" S mirrored (file a open: the defences come first in the list — the control);
+    "W" an instant road among the first 512 of more; "e512" / "e513" / "e512_bare" the edge.
+    roots: "R" → S, "R_swapped" → S_swapped, "R_mirror" → S_mirror, "R_W" → W, "R_e512" → e512, "R_e513" → e513: each is the child
+    with one flat of the side not to move back in hand, so its own list is short."""
+    assert n == 6, "the family is built on 6×6 only"
+    states = {k: from_tps(n, t) for k, t in LONG_LIST_TPS.items()}
+    states["S_swapped"] = swap_colours(states["S"], n)
+    states["S_mirror"] = symmetry_image(states["S"], n, 4)
+    s_images = []
+    for s in range(1, 8):
+        img = symmetry_image(states["S"], n, s)
+        _, res, hit = reply_table(orc, n, img)
+        if (res[:512] == 0).all() and hit[:512].all():
+            s_images.append(s)
+            states[f"S_sym{s}"] = img
+    f3, a3, a1, a2 = 2 * n + 5, 2 * n, 0, n
+    roots = {}
+    for name, child, sq in (("R", "S", f3), ("R_swapped", "S_swapped", f3), ("R_mirror", "S_mirror", a3), ("R_W", "W", a1),
+                            ("R_e512", "e512", a2), ("R_e513", "e513", a1)):
+        root, move = take_back_flat(states[child], n, sq)
+        roots[name] = (root, move, child)
+    edge_roots = {k: from_tps(n, t) for k, t in EDGE_ROOT_TPS.items()}
+    return dict(states=states, roots=roots, edge_roots=edge_roots, s_images=s_images)

@@ -15,6 +15,9 @@ from oracle import oracle
 
 TG_MAX_MOVES = 512
 VARIANTS = ("no_suicide", "draw_is_loss", "min_at_lost", "last_best", "no_early_stop", "reversible_is_ongoing")
+# mistakes about the move-list capacity inside the tree (they show only below a position with more than TG_MAX_MOVES moves):
+# the parent's behaviour, which took the first TG_MAX_MOVES of a longer list for the whole list, and a give-up that is not reported
+CAPACITY_VARIANTS = ("cut_x_test", "silent_give_up")
 TG_DRAW_REVERSIBLE = 6  # the result code of the 50-reversible-plies draw
 FIELDS = ("value", "best", "counts", "moves", "move_values")
 
@@ -23,9 +26,13 @@ class Ref:
     """W, X and the move values on arrays of positions: W(S, L)[i] / X(S, L)[i] is the predicate on the ongoing position S[i]."""
     CHUNK = 2048  # positions expanded at once (bounds the memory of one batch of children)
 
-    def __init__(self, n, variant=None):
-        assert variant is None or variant in VARIANTS
+    def __init__(self, n, variant=None, capacity=TG_MAX_MOVES):
+        """capacity: the longest move list a position INSIDE the tree may have (include/takgpu.h, "Move-list capacity inside the tree":
+        X on a longer list gives up, W searches its first `capacity` moves and gives up if none of them wins); None = no capacity,
+        the exact predicates on whole lists"""
+        assert variant is None or variant in VARIANTS + CAPACITY_VARIANTS
         self.n = n
+        self.capacity = capacity
         self.sb = oracle.state_bytes(n)
         self.variant = variant
         self.nodes = 0  # children generated
@@ -55,44 +62,69 @@ class Ref:
             res = np.where(res == TG_DRAW_REVERSIBLE, 0, res).astype(res.dtype)
         return ch, res
 
+    def lists(self, S):
+        """(moves, counts, cut) as the solver sees them: the whole list up to the capacity; cut = the position has more"""
+        if self.capacity is None:
+            moves, counts = oracle.movegen_full(self.n, S)
+            return moves, counts, np.zeros(len(S), bool)
+        moves, counts = oracle.movegen(self.n, S)
+        cut = counts > self.capacity
+        if self.variant == "cut_x_test":  # the mistake planted: a cut list is taken for the whole list
+            cut = np.zeros(len(S), bool)
+        return moves, np.minimum(counts, self.capacity), cut
+
     def W(self, S, L):
-        """some move wins at once, or leads to an ongoing position that is X within L - 1"""
+        """some move wins at once, or leads to an ongoing position that is X within L - 1.  → (holds, gave up): the moves are tried
+        in order up to the first that wins; gave up = a test on a cut list failed on the way (a cut list of S itself without a win
+        among its first `capacity` moves included)"""
         k = len(S)
         if L <= 0 or k == 0:
-            return np.zeros(k, bool)
+            return np.zeros(k, bool), np.zeros(k, bool)
         if k > self.CHUNK:
-            return np.concatenate([self.W(S[i:i + self.CHUNK], L) for i in range(0, k, self.CHUNK)])
-        moves, counts = oracle.movegen(self.n, S)
-        assert counts.max() <= TG_MAX_MOVES
+            parts = [self.W(S[i:i + self.CHUNK], L) for i in range(0, k, self.CHUNK)]
+            return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+        moves, counts, cut = self.lists(S)
         idx = np.repeat(np.arange(k), counts)
         col = np.arange(len(idx)) - np.repeat(np.cumsum(counts) - counts, counts)
         ch, res = self.play(S[idx], moves[idx, col])
-        out = np.zeros(k, bool)
-        out[idx[self.won(res, self.mover(S)[idx])]] = True
+        win = self.won(res, self.mover(S)[idx])
+        gave_up = np.zeros(len(idx), bool)
+        never = np.iinfo(np.int64).max
+        first = np.full(k, never)  # the first move that wins: the test does not look behind it
+        np.minimum.at(first, idx[win], col[win])
         if L > 1:
-            cand = np.nonzero((res == 0) & ~out[idx])[0]
-            out[idx[cand[self.X(ch[cand], L - 1)]]] = True
-        return out
+            cand = np.nonzero((res == 0) & (col < first[idx]))[0]
+            win[cand], gave_up[cand] = self.X(ch[cand], L - 1)
+            np.minimum.at(first, idx[win], col[win])
+        out = first < never
+        over = cut & ~out
+        seen = gave_up & (col <= first[idx])
+        over[idx[seen]] = True
+        return out, over
 
     def X(self, S, L):
         """every move loses at once, or leads to an ongoing position that is W within L - 1 (move by move: a position leaves
-        the test at its first move that does neither)"""
+        the test at its first move that does neither).  → (holds, gave up): a position whose list is cut fails before its first
+        move and has given up; otherwise gave up = one of the W tests on the way did"""
         k = len(S)
         if L <= 0 or k == 0:
-            return np.zeros(k, bool)
-        moves, counts = oracle.movegen(self.n, S)
-        out = np.ones(k, bool)
+            return np.zeros(k, bool), np.zeros(k, bool)
+        moves, counts, cut = self.lists(S)
+        out, over = ~cut, cut.copy()
+        if self.variant == "silent_give_up":  # the mistake planted: the give-up is not reported
+            over = np.zeros(k, bool)
         m = self.mover(S)
-        alive, j = np.arange(k), 0
+        alive, j = np.nonzero(~cut)[0], 0
         while True:
             alive = alive[counts[alive] > j]
             if not len(alive):
-                return out
+                return out, over
             ch, res = self.play(S[alive], moves[alive, j])
             ok = self.lost_at_once(res, m[alive])
             if L > 1:
                 cand = np.nonzero((res == 0) & ~ok)[0]
-                ok[cand[self.W(ch[cand], L - 1)]] = True
+                ok[cand], sub = self.W(ch[cand], L - 1)
+                over[alive[cand]] |= sub
             out[alive[~ok]] = False
             alive, j = alive[ok], j + 1
 
@@ -109,14 +141,20 @@ class Ref:
         return value, int(moves[hits[-1] if self.variant == "last_best" else hits[0]])
 
     def solve_one(self, s, depth, all_moves):
-        """→ (value, best, moves, move_values).  Level L gives a still unvalued move a the value +L if X(s_a, L - 1), else
-        -L if W(s_a, L - 1): the least k of the definition, found by trying k = 0, 1, … in turn."""
+        """→ (value, best, moves, move_values)"""
+        return self.solve_one_full(s, depth, all_moves)[:4]
+
+    def solve_one_full(self, s, depth, all_moves):
+        """→ (value, best, moves, move_values, gave up).  Level L gives a still unvalued move a the value +L if X(s_a, L - 1), else
+        -L if W(s_a, L - 1): the least k of the definition, found by trying k = 0, 1, … in turn.  gave up = some test of some level
+        that ran failed on a cut list."""
         s = np.ascontiguousarray(s, np.uint8).reshape(1, -1)
         if int(oracle.result(self.n, s)[0]) != 0:
-            return 0, 0, np.zeros(0, np.uint16), []
+            return 0, 0, np.zeros(0, np.uint16), [], False
         moves, counts = oracle.movegen(self.n, s)
         c = int(counts[0])
-        assert c <= TG_MAX_MOVES
+        if c > TG_MAX_MOVES:  # the root's own list is an output row of TG_MAX_MOVES: the call is refused (TG_ERR_INVALID_ARG)
+            raise ValueError(f"the root has {c} moves, more than TG_MAX_MOVES")
         moves = moves[0, :c]
         ch, res = self.play(np.repeat(s, c, axis=0), moves)
         m = self.mover(s).repeat(c)
@@ -124,31 +162,37 @@ class Ref:
         vals[self.lost_at_once(res, m)] = -1
         vals[self.won(res, m)] = 1
         stop_early = not (all_moves or self.variant == "no_early_stop")
+        gave_up = False
         for level in range(1, depth + 1):  # the levels run: L* is the first that decides the position, or depth
             if level > 1:
                 pend = np.nonzero((res == 0) & (vals == 0))[0]
-                vals[pend[self.X(ch[pend], level - 1)]] = level
-                pend = pend[vals[pend] == 0]
-                vals[pend[self.W(ch[pend], level - 1)]] = -level
+                holds, over = self.X(ch[pend], level - 1)
+                vals[pend[holds]] = level
+                gave_up |= bool(over.any())
+                pend = pend[~holds]
+                holds, over = self.W(ch[pend], level - 1)
+                vals[pend[holds]] = -level
+                gave_up |= bool(over.any())
             value, best = self.fold(moves, [int(v) for v in vals])
             if stop_early and value != 0:
                 break
-        return value, best, moves, [int(v) for v in vals]
+        return value, best, moves, [int(v) for v in vals], gave_up
 
     def solve(self, states, depth, all_moves=False):
         states = np.ascontiguousarray(states, np.uint8).reshape(-1, self.sb)
         k = len(states)
         out = dict(value=np.zeros(k, np.int8), best=np.zeros(k, np.uint16), counts=np.zeros(k, np.int32),
                    moves=np.zeros((k, TG_MAX_MOVES), np.uint16), move_values=np.zeros((k, TG_MAX_MOVES), np.int8),
-                   nodes=np.zeros(k, np.uint64))
+                   nodes=np.zeros(k, np.uint64), budget_hit=np.zeros(k, np.uint8))
         for i in range(k):
             before = self.nodes
-            value, best, moves, vals = self.solve_one(states[i], depth, all_moves)
+            value, best, moves, vals, gave_up = self.solve_one_full(states[i], depth, all_moves)
             c = len(moves)
             out["value"][i], out["best"][i], out["counts"][i] = value, best, c
             out["moves"][i, :c] = moves
             out["move_values"][i, :c] = vals
             out["nodes"][i] = self.nodes - before
+            out["budget_hit"][i] = gave_up
         return out
 
 
@@ -166,6 +210,29 @@ def compare(ref, got, budget_free=True):
             bad.append(f"{f}: {len(rows)} rows differ, first {int(rows[0])}: expected {a[rows[0]].ravel()[:12]} got {b[rows[0]].ravel()[:12]}")
     if budget_free and "budget_hit" in got and np.asarray(got["budget_hit"]).any():
         bad.append(f"budget_hit set for {int(np.count_nonzero(got['budget_hit']))} positions")
+    return bad
+
+
+def compare_with_give_up(ref, got):
+    """the comparison of the GPU tests on positions above a move list longer than TG_MAX_MOVES: every field of FIELDS and budget_hit
+    equal, row for row (the node budget is set so high that only a cut list gives up)"""
+    bad = compare(ref, got, budget_free=False)
+    a, b = np.asarray(ref["budget_hit"]).astype(bool), np.asarray(got["budget_hit"]).astype(bool)
+    if a.shape != b.shape or (a != b).any():
+        bad.append(f"budget_hit: expected {a.astype(int)} got {b.astype(int)}")
+    return bad
+
+
+def sound(exact, got, depth):
+    """the promise of include/takgpu.h on every row: a non-zero value has the sign of the exact value (the whole lists, no capacity,
+    at the same depth) and a distance not below it — per position and per move.  → the list of violations"""
+    bad = []
+    for f in ("value", "move_values"):
+        e, g = np.asarray(exact[f]).astype(np.int64), np.asarray(got[f]).astype(np.int64)
+        wrong = (g != 0) & ((np.sign(g) != np.sign(e)) | (np.abs(g) < np.abs(e)))
+        if wrong.any():
+            r = np.argwhere(wrong)[0]
+            bad.append(f"{f}: {int(wrong.sum())} unsound entries, first at {tuple(int(x) for x in r)}: exact {e[tuple(r)]} got {g[tuple(r)]}")
     return bad
 
 
