@@ -1,5 +1,5 @@
-// net.hip — host side of the network: tensor intake in tch/libtorch layout, BatchNorm folding,
-// re-layout for the MFMA kernels, and the forward schedule (one kernel per conv layer, heads,
+// net.hip — host side of the network: tensor intake in tch/libtorch layout, upload of the folded and
+// re-laid-out weights (the packers are net_pack.h), the head plan, and the forward schedule (one kernel per conv layer, heads,
 // softmax) on the engine stream.  Replaces Network<N> of reference alpha-tak/src/model/network.rs:26-35
 // and the concrete Net5 / Net6 (model/net5.rs, net6.rs, res_block.rs) without any tch type.
 #include <climits>
@@ -9,6 +9,7 @@
 
 #include "engine.h"
 #include "kernels.h"
+#include "net_pack.h"
 #include "softmax.cuh"
 #include "rng.cuh"
 
@@ -20,8 +21,26 @@ struct ConvLayer {
     int cout = 0, cout_pad = 0;
 };
 
+// What the head of a forward does for this (topology, precision): decided once, at the end of net_finalize
+enum HeadKind { HEAD_CONV_F32, HEAD_FC_F32, HEAD_FC_SPLIT };
+struct HeadPlan {
+    HeadKind kind = HEAD_CONV_F32;  // conv head / exact-f32 FC (k_fc_ring, k_fc_small, k_gemm) / split-bf16 FC (k_fc_s3b, k_fc_s3_ring)
+    bool conv_in_tower = false;     // the conv head is computed inside the split tower (TowerS3Params.head_*)
+    bool split_act = false;         // the split tower writes split activations (its FC or conv head is in use): the value head reads them so
+    bool frag_act = false;          // the exact tower writes the FC's fragment order (TowerParams.frag_out)
+    int ld = 0;                     // logits row stride: the FC's padded outputs, nsq · CoutP of the conv head
+    bool value_col = false;         // the value head rides in padding column P of the policy FC (logit P = value pre-activation)
+    bool search_logits = false;     // logits-only forwards are offered to the search (net_fc_logits); not on split tower + f32 FC
+    bool stats = false;             // the FC emits block-wise softmax statistics (softmax.cuh) into Net.fc_stats
+    int stat_blocks = 0;            // FC_STAT_BLOCKS (11) with stats, else 0
+    int stat_stride = 0;            // pairs per row of fc_stats: the blocks, then {value pre-activation, 0}
+    const void* w = nullptr;        // FC weights: Wp [K/16][ld][16] f32 / k_fc_s3b's split layout
+    const float* b = nullptr;       // FC bias padded to ld
+    const void* w_ring = nullptr;   // the ring kernels' copy (k_fc_ring's lane order / k_fc_s3_ring's layout, nullptr: it has none)
+};
+
 struct Net {
-    std::map<std::string, std::vector<float>> tensors;  // as given (tch layouts)
+    TensorMap tensors;  // as given (tch layouts)
     bool ready = false;
     int F = 0, R = 0, cin = 0, cin_pad = 0;
     ConvLayer conv0;
@@ -29,18 +48,12 @@ struct Net {
     ConvLayer policy_conv;            // TG_HEAD_CONV
     DevBuf policy_w, policy_b;        // TG_HEAD_FC5: Wp [K/16][NP][16]
     DevBuf policy_w_lin;              // the same, every (chunk, tile) block of 16 columns in the MFMA fragment's lane order (k_fc_ring's LDS-DMA source)
-    int policy_np = 0;                // padded FC outputs
-    bool value_in_fc = false;         // the value head rides in padding column P of the policy FC (logit P = value pre-activation)
     DevBuf value_w;                   // [nsq*F] in NHWC order
     float value_b = 0.0f;
+    HeadPlan head;
     // activations (max_batch positions)
     DevBuf x, y, logits, planes_nhwc, planes_nchw;
-    DevBuf s3_fc_ring;                // the same weights in k_fc_s3_ring's layout [chunk of 32][tile 0 … 98][hi|lo][lane] (full batches)
-    bool s3_fc_ring_on = false;
-    DevBuf fc_stats;                  // [max_batch][fc_stat_blocks][2]: block-wise softmax statistics of the policy FC (softmax.cuh)
-    bool fc_stats_on = false;
-    int fc_stat_blocks = 0;           // FC_STAT_BLOCKS (11) on the exact path, s3_np / 112 on the split-bf16 FC
-    int fc_stat_stride = 0;           // pairs per row of fc_stats: the exact path appends {value pre-activation, 0}
+    DevBuf fc_stats;                  // [max_batch][head.stat_stride][2]: block-wise softmax statistics of the policy FC (softmax.cuh)
     FcGatherArgs gather{};            // set by the search (net_set_gather): logits-only forwards of the exact FC write the
     bool gather_on = false;           // children's logits of every leaf instead of the logits rows
     bool fused = false;  // whole tower in one launch (k_tower)
@@ -59,10 +72,8 @@ struct Net {
     std::vector<DevBuf> s3_w;
     DevBuf s3_w0_board;    // conv0 over the board planes only, split fragments with one 32-channel chunk (TowerS3Params.cb)
     DevBuf s3_head;        // conv policy head weights, split (computed inside k_tower_s3)
-    bool s3_head_on = false;
-    DevBuf s3_fc, s3_fc_b; // policy FC weights (split) and bias padded to s3_np
-    int s3_np = 0;         // padded outputs of the split FC
-    bool s3_fc_on = false; // FC head on the split path (tower writes split activations)
+    DevBuf s3_fc, s3_fc_b; // policy FC weights (split) and bias padded to round_up(P, FC_S3_COLS)
+    DevBuf s3_fc_ring;     // the same weights in k_fc_s3_ring's layout [chunk of 32][tile 0 … 98][hi|lo][lane] (full batches)
     // tg_eval_examples: a slice's examples (states, {offset, n_moves, result} records, packed move / visit lists), its rows and
     // target entropies, and the call's sums ({Σ loss_p, Σ loss_z, Σ entropy} f64, {top1, sign_ok, decided} u64)
     DevBuf ev_states, ev_rec, ev_moves, ev_visits, ev_rows, ev_ent, ev_acc;
@@ -101,8 +112,6 @@ static void prof_collect(Net* n) {  // the stream must be idle
 
 void net_destroy(Net* n) { delete n; }
 
-static int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 int net_create(TgEngine* e) {
     Net* n = new Net();
     e->net = n;
@@ -122,112 +131,29 @@ int net_set_tensor(TgEngine* e, const char* name, const float* data, size_t coun
 }
 
 bool net_ready(const TgEngine* e) { return e && e->net && e->net->ready; }
-const std::map<std::string, std::vector<float>>* net_tensors(const TgEngine* e) { return e && e->net ? &e->net->tensors : nullptr; }
+const TensorMap* net_tensors(const TgEngine* e) { return e && e->net ? &e->net->tensors : nullptr; }
 
 namespace {
 
-struct Folded {
-    std::vector<float> w, b;  // OIHW weights scaled per output channel, bias
-};
-
-const std::vector<float>* find(Net* n, const std::string& name, size_t want, std::string& err) {
-    auto it = n->tensors.find(name);
-    if (it == n->tensors.end()) { err = "missing tensor " + name; return nullptr; }
-    if (it->second.size() != want) {
-        err = "tensor " + name + " has " + std::to_string(it->second.size()) + " elements, expected " + std::to_string(want);
-        return nullptr;
-    }
-    return &it->second;
+template <class T>
+hipError_t upload(DevBuf& b, const std::vector<T>& v) {
+    hipError_t e = b.ensure(v.size() * sizeof(T));
+    return e != hipSuccess ? e : hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
-// conv (O,I,3,3)+bias followed by BatchNorm in eval mode (running stats, eps = 1e-5, tch default):
-// y = (conv(x) + b - mean) * gamma / sqrt(var + eps) + beta  →  w' = w*s, b' = (b - mean)*s + beta
-bool fold_conv_bn(Net* n, const std::string& conv, const std::string& bn, int O, int I, Folded& out, std::string& err) {
-    auto w = find(n, conv + ".weight", (size_t)O * I * 9, err);
-    auto b = w ? find(n, conv + ".bias", O, err) : nullptr;
-    if (!w || !b) return false;
-    out.w = *w;
-    out.b = *b;
-    if (bn.empty()) return true;
-    auto g = find(n, bn + ".weight", O, err);
-    auto be = g ? find(n, bn + ".bias", O, err) : nullptr;
-    auto mu = be ? find(n, bn + ".running_mean", O, err) : nullptr;
-    auto var = mu ? find(n, bn + ".running_var", O, err) : nullptr;
-    if (!var) return false;
-    for (int o = 0; o < O; o++) {
-        float s = (*g)[o] / std::sqrt((*var)[o] + 1e-5f);
-        for (int k = 0; k < I * 9; k++) out.w[(size_t)o * I * 9 + k] *= s;
-        out.b[o] = ((*b)[o] - (*mu)[o]) * s + (*be)[o];
-    }
-    return true;
-}
-
-// OIHW → Wp[(tap*Ipad + c)/16][CoutP][(tap*Ipad + c)%16], tap = ky*3 + kx, zero padded
-// last_t = 2 / 3: the real channels of the last 16-channel chunk go to positions 4·(i / last_t) + i % last_t
-// (conv_mainloop.cuh conv_last_chunk_perm: layer 0 of the fused towers); 4 = channel order
 hipError_t upload_conv(const Folded& f, int O, int I, int Ipad, ConvLayer& L, int last_t = 4) {
-    int OP = round_up(O, 64);
-    size_t K = (size_t)9 * Ipad;
-    std::vector<float> wp(K * OP, 0.0f), bp(OP, 0.0f);
-    for (int o = 0; o < O; o++) {
-        bp[o] = f.b[o];
-        for (int c = 0; c < I; c++)
-            for (int tap = 0; tap < 9; tap++) {
-                int pos = c & 15;
-                if (last_t < 4 && c >= Ipad - 16) { const int i = c - (Ipad - 16); pos = 4 * (i / last_t) + i % last_t; }
-                size_t k = (size_t)tap * Ipad + (c & ~15) + pos;
-                wp[((k >> 4) * OP + o) * 16 + (k & 15)] = f.w[((size_t)o * I + c) * 9 + tap];
-            }
-    }
-    L.cin_pad = Ipad; L.cout = O; L.cout_pad = OP;
-    hipError_t e = L.w.ensure(wp.size() * 4);
-    if (e != hipSuccess) return e;
-    e = L.b.ensure(bp.size() * 4);
-    if (e != hipSuccess) return e;
-    e = hipMemcpy(L.w.p, wp.data(), wp.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return e;
-    return hipMemcpy(L.b.p, bp.data(), bp.size() * 4, hipMemcpyHostToDevice);
+    std::vector<float> wp, bp;
+    pack_conv(f, O, I, Ipad, last_t, wp, bp);
+    L.cin_pad = Ipad; L.cout = O; L.cout_pad = (int)bp.size();
+    hipError_t e = upload(L.w, wp);
+    return e != hipSuccess ? e : upload(L.b, bp);
 }
 
-uint16_t f32_to_bf16(float x) {  // round to nearest even, as v_cvt_pk_bf16_f32
-    uint32_t u;
-    std::memcpy(&u, &x, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)(u >> 16);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-float bf16_to_f32(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float x;
-    std::memcpy(&x, &u, 4);
-    return x;
-}
-
-// OIHW (BN folded) → [chunk = tap·KC + kc][cout tile][hi|lo][q][cout][8 bf16], channel = 32·kc + 8q + j, zero padded
-hipError_t upload_conv_s3(const Folded& f, int O, int I, int KC, DevBuf& buf, int OP = 0) {
-    if (!OP) OP = O;  // output channels of the fragment layout (multiple of 16), O of them real
-    std::vector<uint16_t> w((size_t)9 * KC * OP * 64, 0);
-    for (int tap = 0; tap < 9; tap++)
-        for (int kc = 0; kc < KC; kc++)
-            for (int o = 0; o < O; o++)
-                for (int q = 0; q < 4; q++)
-                    for (int j = 0; j < 8; j++) {
-                        int c = 32 * kc + 8 * q + j;
-                        if (c >= I) continue;
-                        float v = f.w[((size_t)o * I + c) * 9 + tap];
-                        uint16_t hi = f32_to_bf16(v);
-                        uint16_t lo = f32_to_bf16(v - bf16_to_f32(hi));
-                        // [chunk][tile of 16 couts][hi|lo][q][cout in tile][8 bf16].  A wave computes two tiles = 32 output channels;
-                        // the MFMA leaves rows 4q' … 4q' + 3 of a tile in lane group q', so channel 8q' + 4t + i of the 32 goes to
-                        // row 4q' + i of tile t: lane group q' then holds channels 8q' … 8q' + 7 — one 16-byte slot of the split image
-                        const int o32 = o & 31, tile = (o >> 5) * 2 + ((o32 >> 2) & 1), row = (o32 >> 3) * 4 + (o32 & 3);
-                        size_t slot = (((((size_t)tap * KC + kc) * (OP / 16) + tile) * 2) * 4 + q) * 16 + row;
-                        w[slot * 8 + j] = hi;
-                        w[(slot + 64) * 8 + j] = lo;
-                    }
-    hipError_t e = buf.ensure(w.size() * 2);
-    if (e != hipSuccess) return e;
-    return hipMemcpy(buf.p, w.data(), w.size() * 2, hipMemcpyHostToDevice);
+// tile slot → square table of a halo tower's workgroup: pw positions at a stride of ps cells
+hipError_t upload_halo_map(int n, int pw, int ps, DevBuf& buf) {
+    std::vector<uint32_t> map((size_t)((pw * n * n + 15) / 16) * 16);
+    tower_halo_slotmap(n, pw, ps, map.data());
+    return upload(buf, map);
 }
 
 }  // namespace
@@ -236,91 +162,55 @@ int net_finalize(TgEngine* e) {
     if (!e || !e->net) return fail(TG_ERR_STATE, "engine has no network (evaluator is not TG_EVAL_RESNET)");
     TG_HIP(hipSetDevice(e->cfg.device));
     Net* n = e->net;
-    const int F = n->F, R = n->R, nsq = e->g.nsq;
+    const int F = n->F, R = n->R, N = e->g.n, nsq = e->g.nsq, P = e->policy_size;
+    const size_t K = (size_t)F * nsq;
+    const bool fc_head = e->cfg.policy_head == TG_HEAD_FC5;
+    // fold: every (conv, bn) pair once, every tensor looked up in the order a missing one is reported
     std::string err;
-    Folded f;
-    if (!fold_conv_bn(n, "conv0", "bn0", F, n->cin, f, err)) return fail(TG_ERR_WEIGHTS, err);
-    TG_HIP(upload_conv(f, F, n->cin, n->cin_pad, n->conv0));
-    n->res1.clear(); n->res2.clear();
-    n->res1.resize(R); n->res2.resize(R);
+    Folded f0, fhead;
+    std::vector<Folded> fres(2 * R);  // res i: conv1 + bn1 at 2i, conv2 + bn2 at 2i + 1
+    if (!fold_conv_bn(n->tensors, "conv0", "bn0", F, n->cin, f0, err)) return fail(TG_ERR_WEIGHTS, err);
+    for (int l = 0; l < 2 * R; l++) {
+        const std::string p = "res" + std::to_string(l / 2), k = std::to_string(1 + l % 2);
+        if (!fold_conv_bn(n->tensors, p + ".conv" + k, p + ".bn" + k, F, F, fres[l], err)) return fail(TG_ERR_WEIGHTS, err);
+    }
+    const std::vector<float>*polw = nullptr, *polb = nullptr;
+    if (fc_head) {
+        polw = find(n->tensors, "policy.weight", (size_t)P * K, err);
+        polb = polw ? find(n->tensors, "policy.bias", P, err) : nullptr;
+        if (!polb) return fail(TG_ERR_WEIGHTS, err);
+    } else if (!fold_conv_bn(n->tensors, "policy", "", P / nsq, F, fhead, err)) return fail(TG_ERR_WEIGHTS, err);
+    auto wv = find(n->tensors, "value.weight", K, err);
+    auto bv = wv ? find(n->tensors, "value.bias", 1, err) : nullptr;
+    if (!bv) return fail(TG_ERR_WEIGHTS, err);
+    const bool s3 = n->precision == TG_PRECISION_BF16X3;
+    n->s3 = false;
+    if (s3 && (!tower_s3_supported(N, F) || 1 + 2 * R > 48 || n->cin > 96))
+        return fail(TG_ERR_INVALID_ARG, "TG_PRECISION_BF16X3 supports 5x5 with 64 or 128 filters and 6x6 with 128 filters");
+    // the FC head's geometry: padded outputs on either precision, which FC runs, and whether the padding leaves the value
+    // head a column (decided here, once, for every layout below)
+    const int np = fc_head ? fc_padded_cols(K, P) : 0, np3 = s3 ? round_up(P, FC_S3_COLS) : 0;
+    const bool split_fc = fc_head && s3 && fc_s3_supported((int)K, np3);
+    const bool value_col = fc_head && np > P && (!split_fc || np3 > P);
+    const FcColumns fc{fc_head ? polw->data() : nullptr, fc_head ? polb->data() : nullptr, value_col ? wv->data() : nullptr, (*bv)[0], P, F, nsq};
+
+    // exact-path weights
+    TG_HIP(upload_conv(f0, F, n->cin, n->cin_pad, n->conv0));
+    n->res1 = std::vector<ConvLayer>(R); n->res2 = std::vector<ConvLayer>(R);
     for (int i = 0; i < R; i++) {
-        std::string p = "res" + std::to_string(i);
-        if (!fold_conv_bn(n, p + ".conv1", p + ".bn1", F, F, f, err)) return fail(TG_ERR_WEIGHTS, err);
-        TG_HIP(upload_conv(f, F, F, F, n->res1[i]));
-        if (!fold_conv_bn(n, p + ".conv2", p + ".bn2", F, F, f, err)) return fail(TG_ERR_WEIGHTS, err);
-        TG_HIP(upload_conv(f, F, F, F, n->res2[i]));
+        TG_HIP(upload_conv(fres[2 * i], F, F, F, n->res1[i]));
+        TG_HIP(upload_conv(fres[2 * i + 1], F, F, F, n->res2[i]));
     }
-    const int P = e->policy_size;
-    if (e->cfg.policy_head == TG_HEAD_CONV) {
-        int ch = P / nsq;
-        if (!fold_conv_bn(n, "policy", "", ch, F, f, err)) return fail(TG_ERR_WEIGHTS, err);
-        TG_HIP(upload_conv(f, ch, F, F, n->policy_conv));
-    } else {
-        // Linear [P, F*nsq] over the NCHW flattening c*nsq + sq (net5.rs:86 view) → K order sq*F + c
-        size_t K = (size_t)F * nsq;
-        auto w = find(n, "policy.weight", (size_t)P * K, err);
-        auto b = w ? find(n, "policy.bias", P, err) : nullptr;
-        if (!b) return fail(TG_ERR_WEIGHTS, err);
-        // padded to 1664 columns (the FC kernels use the first 99 tiles = 1584 of them, softmax.cuh; the generic k_gemm and
-        // k_fc_small want multiples of 64 / 32); shapes with K % 64 != 0 go through k_gemm
-        int NP = (K % 64 == 0) ? round_up(P, 208) : round_up(P, 64);
-        std::vector<float> wp(K * NP, 0.0f), bp(NP, 0.0f);
-        for (int o = 0; o < P; o++) {
-            bp[o] = (*b)[o];
-            for (int c = 0; c < F; c++)
-                for (int sq = 0; sq < nsq; sq++) {
-                    size_t k = (size_t)sq * F + c;
-                    wp[((k >> 4) * NP + o) * 16 + (k & 15)] = (*w)[(size_t)o * K + (size_t)c * nsq + sq];
-                }
-        }
-        // the FC is padded anyway: column P carries the value head (Linear(F·nsq → 1), net5.rs:62), so the value costs no
-        // kernel of its own — the softmax kernel applies the tanh
-        n->value_in_fc = false;
-        {
-            auto wv = find(n, "value.weight", K, err);
-            auto bv = wv ? find(n, "value.bias", 1, err) : nullptr;
-            if (!bv) return fail(TG_ERR_WEIGHTS, err);
-            if (NP > P) {
-                bp[P] = (*bv)[0];
-                for (int c = 0; c < F; c++)
-                    for (int sq = 0; sq < nsq; sq++) {
-                        size_t k = (size_t)sq * F + c;
-                        wp[((k >> 4) * NP + P) * 16 + (k & 15)] = (*wv)[(size_t)c * nsq + sq];
-                    }
-                n->value_in_fc = true;
-            }
-        }
-        n->policy_np = NP;
-        TG_HIP(n->policy_w.ensure(wp.size() * 4));
-        TG_HIP(n->policy_b.ensure(bp.size() * 4));
-        TG_HIP(hipMemcpy(n->policy_w.p, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
-        {   // block (chunk, tile): slot q·16 + r holds the 4 floats (k = 16·chunk + 4q … 4q + 3) of column 16·tile + r
-            std::vector<float> wl(wp.size());
-            const size_t tiles = (size_t)NP / 16;
-            for (size_t c = 0; c < K / 16; c++)
-                for (size_t t = 0; t < tiles; t++)
-                    for (size_t r = 0; r < 16; r++)
-                        for (size_t qq = 0; qq < 4; qq++)
-                            for (size_t u = 0; u < 4; u++)
-                                wl[((c * tiles + t) * 64 + qq * 16 + r) * 4 + u] = wp[((c * NP + t * 16 + r) * 4 + qq) * 4 + u];
-            TG_HIP(n->policy_w_lin.ensure(wl.size() * 4));
-            TG_HIP(hipMemcpy(n->policy_w_lin.p, wl.data(), wl.size() * 4, hipMemcpyHostToDevice));
-        }
-        TG_HIP(hipMemcpy(n->policy_b.p, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
-    }
-    {
-        size_t K = (size_t)F * nsq;
-        auto w = find(n, "value.weight", K, err);
-        auto b = w ? find(n, "value.bias", 1, err) : nullptr;
-        if (!b) return fail(TG_ERR_WEIGHTS, err);
-        std::vector<float> wv(K);
-        for (int c = 0; c < F; c++)
-            for (int sq = 0; sq < nsq; sq++) wv[(size_t)sq * F + c] = (*w)[(size_t)c * nsq + sq];
-        n->value_b = (*b)[0];
-        TG_HIP(n->value_w.ensure(K * 4));
-        TG_HIP(hipMemcpy(n->value_w.p, wv.data(), K * 4, hipMemcpyHostToDevice));
-    }
-    n->fused = tower_supported(e->g.n, F, n->cin_pad) && 1 + 2 * R <= 48;
+    if (fc_head) {
+        const std::vector<float> wp = pack_fc(fc, np);
+        TG_HIP(upload(n->policy_w, wp));
+        TG_HIP(upload(n->policy_w_lin, pack_fc_lanes(wp, np)));
+        TG_HIP(upload(n->policy_b, fc.bias(np)));
+    } else TG_HIP(upload_conv(fhead, P / nsq, F, F, n->policy_conv));
+    n->value_b = (*bv)[0];
+    TG_HIP(upload(n->value_w, pack_value(wv->data(), F, nsq)));
+
+    n->fused = tower_supported(N, F, n->cin_pad) && 1 + 2 * R <= 48;
     if (n->fused) {
         TowerParams& T = n->tower;
         T.nlayers = 1 + 2 * R; T.cin_pad = n->cin_pad; T.F = F;
@@ -329,44 +219,15 @@ int net_finalize(TgEngine* e) {
         const int tail = n->cin - (n->cin_pad - 16);
         T.cin_last_t = (tail > 0 && tail <= 12) ? (tail + 3) / 4 : 4;
         if (T.cin_last_t < 2) T.cin_last_t = 4;
-        {
-            Folded f0;
-            if (!fold_conv_bn(n, "conv0", "bn0", F, n->cin, f0, err)) return fail(TG_ERR_WEIGHTS, err);
-            TG_HIP(upload_conv(f0, F, n->cin, n->cin_pad, n->conv0_tower, T.cin_last_t));
-        }
+        TG_HIP(upload_conv(f0, F, n->cin, n->cin_pad, n->conv0_tower, T.cin_last_t));
         T.w[0] = n->conv0_tower.w.as<float>(); T.b[0] = n->conv0.b.as<float>();
-        // Constant planes as a bias (kernels.h TowerParams.cb; states entry): conv0 over the board planes, and per constant
-        // plane and border class the sum of its folded weights over the taps that stay on the board (tap order, f32)
+        // Constant planes as a bias (kernels.h TowerParams.cb; states entry): conv0 over the board planes, and the table S
         T.cb = 0; T.cb_cin_pad = 32; T.cb_last_t = 3; T.w0_board = nullptr; T.cplane_sums = nullptr;
-        {
-            const int N = e->g.n, bc = board_channels(N), nconst = n->cin - bc;
-            if (!env_on("TG_NO_CONST_BIAS") && bc > 16 && bc <= 28 && nconst > 0) {
-                Folded f0, fb;
-                if (!fold_conv_bn(n, "conv0", "bn0", F, n->cin, f0, err)) return fail(TG_ERR_WEIGHTS, err);
-                fb.b = f0.b;
-                fb.w.resize((size_t)F * bc * 9);
-                for (int o = 0; o < F; o++)
-                    for (int c = 0; c < bc; c++)
-                        for (int tap = 0; tap < 9; tap++) fb.w[((size_t)o * bc + c) * 9 + tap] = f0.w[((size_t)o * n->cin + c) * 9 + tap];
-                TG_HIP(upload_conv(fb, F, bc, T.cb_cin_pad, n->conv0_board, T.cb_last_t));
-                std::vector<float> S((size_t)nconst * 9 * F, 0.0f);
-                for (int pl = 0; pl < nconst; pl++)
-                    for (int cls = 0; cls < 9; cls++) {
-                        const int cy = cls / 3, cx = cls % 3;  // 0: first row / column, 1: interior, 2: last
-                        for (int o = 0; o < F; o++) {
-                            float sum = 0.0f;
-                            for (int tap = 0; tap < 9; tap++) {
-                                const int dy = tap / 3 - 1, dx = tap % 3 - 1;
-                                if ((cy == 0 && dy < 0) || (cy == 2 && dy > 0) || (cx == 0 && dx < 0) || (cx == 2 && dx > 0)) continue;
-                                sum += f0.w[((size_t)o * n->cin + bc + pl) * 9 + tap];
-                            }
-                            S[((size_t)pl * 9 + cls) * F + o] = sum;
-                        }
-                    }
-                TG_HIP(n->cplane_sums.ensure(S.size() * 4));
-                TG_HIP(hipMemcpy(n->cplane_sums.p, S.data(), S.size() * 4, hipMemcpyHostToDevice));
-                T.cb = 1; T.w0_board = n->conv0_board.w.as<float>(); T.cplane_sums = n->cplane_sums.as<float>();
-            }
+        const int bc = board_channels(N), nconst = n->cin - bc;
+        if (!env_on("TG_NO_CONST_BIAS") && bc > 16 && bc <= 28 && nconst > 0) {
+            TG_HIP(upload_conv(restrict_to_board(f0, F, n->cin, bc), F, bc, T.cb_cin_pad, n->conv0_board, T.cb_last_t));
+            TG_HIP(upload(n->cplane_sums, pack_cplane_sums(f0, F, n->cin, bc)));
+            T.cb = 1; T.w0_board = n->conv0_board.w.as<float>(); T.cplane_sums = n->cplane_sums.as<float>();
         }
         for (int i = 0; i < R; i++) {
             T.w[1 + 2 * i] = n->res1[i].w.as<float>(); T.b[1 + 2 * i] = n->res1[i].b.as<float>();
@@ -374,7 +235,7 @@ int net_finalize(TgEngine* e) {
         }
         T.slotmap = nullptr; T.halo_pw = 0; T.halo_ps = 0;
         T.split_flags = nullptr; T.split_err = nullptr;
-        if (T.cb && (F == 128 || (F == 64 && e->g.n == 5))) {  // small batches split a position over several workgroups (k_tower_split)
+        if (T.cb && (F == 128 || (F == 64 && N == 5))) {  // small batches split a position over several workgroups (k_tower_split)
             TG_HIP(n->split_ctl.ensure((size_t)TOWER_SPLIT_CTL_WORDS * 4));
             TG_HIP(hipMemset(n->split_ctl.p, 0, (size_t)TOWER_SPLIT_CTL_WORDS * 4));
             TG_HIP(n->split_buf.ensure((size_t)2 * TOWER_SPLIT_MAX_BATCH * nsq * F * 4));
@@ -383,154 +244,76 @@ int net_finalize(TgEngine* e) {
         }
         // FC-head networks whose value head rides in the FC's padding column: nothing but the policy FC reads the tower's
         // output, so it is written in the FC's fragment order
-        T.frag_out = (e->cfg.policy_head == TG_HEAD_FC5 && n->value_in_fc && fc_frag_supported(nsq * F, n->policy_np) &&
-                      !env_on("TG_NO_FRAG_OUT")) ? 1 : 0;
+        T.frag_out = (value_col && fc_frag_supported(nsq * F, np) && !env_on("TG_NO_FRAG_OUT")) ? 1 : 0;
         int pw, ps;
-        if (tower_halo_geometry(e->g.n, F, &pw, &ps)) {
-            std::vector<uint32_t> map((size_t)((pw * nsq + 15) / 16) * 16);
-            tower_halo_slotmap(e->g.n, pw, ps, map.data());
-            TG_HIP(n->halo_map.ensure(map.size() * 4));
-            TG_HIP(hipMemcpy(n->halo_map.p, map.data(), map.size() * 4, hipMemcpyHostToDevice));
+        if (tower_halo_geometry(N, F, &pw, &ps)) {
+            TG_HIP(upload_halo_map(N, pw, ps, n->halo_map));
             T.slotmap = n->halo_map.as<uint32_t>(); T.halo_pw = pw; T.halo_ps = ps;
         }
     }
-    n->s3 = false;
-    if (n->precision == TG_PRECISION_BF16X3) {
-        if (!tower_s3_supported(e->g.n, F) || 1 + 2 * R > 48 || n->cin > 96)
-            return fail(TG_ERR_INVALID_ARG, "TG_PRECISION_BF16X3 supports 5x5 with 64 or 128 filters and 6x6 with 128 filters");
+    HeadPlan H;
+    if (s3) {
         TowerS3Params& T = n->tower_s3;
         T.nlayers = 1 + 2 * R; T.cin_pad = n->cin_pad; T.F = F;
-        n->s3_w.clear();
-        n->s3_w.resize(T.nlayers);
-        Folded g;
-        if (!fold_conv_bn(n, "conv0", "bn0", F, n->cin, g, err)) return fail(TG_ERR_WEIGHTS, err);
-        TG_HIP(upload_conv_s3(g, F, n->cin, 3, n->s3_w[0]));
+        n->s3_w = std::vector<DevBuf>(T.nlayers);
+        TG_HIP(upload(n->s3_w[0], pack_conv_s3(f0, F, n->cin, 3)));
         T.w[0] = n->s3_w[0].p; T.b[0] = n->conv0.b.as<float>();
-        for (int i = 0; i < R; i++) {
-            std::string p = "res" + std::to_string(i);
-            if (!fold_conv_bn(n, p + ".conv1", p + ".bn1", F, F, g, err)) return fail(TG_ERR_WEIGHTS, err);
-            TG_HIP(upload_conv_s3(g, F, F, F / 32, n->s3_w[1 + 2 * i]));
-            if (!fold_conv_bn(n, p + ".conv2", p + ".bn2", F, F, g, err)) return fail(TG_ERR_WEIGHTS, err);
-            TG_HIP(upload_conv_s3(g, F, F, F / 32, n->s3_w[2 + 2 * i]));
-            T.w[1 + 2 * i] = n->s3_w[1 + 2 * i].p; T.b[1 + 2 * i] = n->res1[i].b.as<float>();
-            T.w[2 + 2 * i] = n->s3_w[2 + 2 * i].p; T.b[2 + 2 * i] = n->res2[i].b.as<float>();
+        for (int l = 1; l <= 2 * R; l++) {
+            TG_HIP(upload(n->s3_w[l], pack_conv_s3(fres[l - 1], F, F, F / 32)));
+            T.w[l] = n->s3_w[l].p; T.b[l] = (l % 2 ? n->res1[(l - 1) / 2] : n->res2[(l - 1) / 2]).b.as<float>();
         }
         // constant planes as a bias on the split towers too: the f32 table S of the exact path, conv0 restricted to the board planes
         T.cb = 0; T.w0_board = nullptr; T.cplane_sums = nullptr;
         if (n->fused && n->tower.cb) {
-            const int bc = board_channels(e->g.n);
-            Folded fb, g0;
-            if (!fold_conv_bn(n, "conv0", "bn0", F, n->cin, g0, err)) return fail(TG_ERR_WEIGHTS, err);
-            fb.b = g0.b;
-            fb.w.resize((size_t)F * bc * 9);
-            for (int o = 0; o < F; o++)
-                for (int c = 0; c < bc; c++)
-                    for (int tap = 0; tap < 9; tap++) fb.w[((size_t)o * bc + c) * 9 + tap] = g0.w[((size_t)o * n->cin + c) * 9 + tap];
-            TG_HIP(upload_conv_s3(fb, F, bc, 1, n->s3_w0_board));
+            const int bc = board_channels(N);
+            TG_HIP(upload(n->s3_w0_board, pack_conv_s3(restrict_to_board(f0, F, n->cin, bc), F, bc, 1)));
             T.cb = 1; T.w0_board = n->s3_w0_board.p; T.cplane_sums = n->cplane_sums.as<float>();
         }
         T.slotmap = nullptr; T.halo_ps = 0;
         int pw3, ps3;
-        if (tower_s3_halo_geometry(e->g.n, F, &pw3, &ps3)) {
-            std::vector<uint32_t> map((size_t)((pw3 * nsq + 15) / 16) * 16);
-            tower_halo_slotmap(e->g.n, pw3, ps3, map.data());
-            TG_HIP(n->s3_halo_map.ensure(map.size() * 4));
-            TG_HIP(hipMemcpy(n->s3_halo_map.p, map.data(), map.size() * 4, hipMemcpyHostToDevice));
+        if (tower_s3_halo_geometry(N, F, &pw3, &ps3)) {
+            TG_HIP(upload_halo_map(N, pw3, ps3, n->s3_halo_map));
             T.slotmap = n->s3_halo_map.as<uint32_t>(); T.halo_ps = ps3;
         }
-        n->s3 = true;
-        n->s3_fc_on = false;
         T.head_w = nullptr; T.head_b = nullptr; T.head_out = nullptr; T.head_cout = 0;
-        n->s3_head_on = false;
-        if (e->cfg.policy_head == TG_HEAD_CONV && n->policy_conv.cout_pad % 32 == 0) {
-            const int ch = P / nsq;
-            if (!fold_conv_bn(n, "policy", "", ch, F, g, err)) return fail(TG_ERR_WEIGHTS, err);
-            TG_HIP(upload_conv_s3(g, ch, F, F / 32, n->s3_head, n->policy_conv.cout_pad));
+        if (!fc_head && n->policy_conv.cout_pad % 32 == 0) {
+            TG_HIP(upload(n->s3_head, pack_conv_s3(fhead, P / nsq, F, F / 32, n->policy_conv.cout_pad)));
             T.head_w = n->s3_head.p; T.head_b = n->policy_conv.b.as<float>(); T.head_cout = n->policy_conv.cout_pad;
-            n->s3_head_on = true;
+            H.conv_in_tower = true;
         }
-        n->s3_np = round_up(P, FC_S3_COLS);
-        if (e->cfg.policy_head == TG_HEAD_FC5 && fc_s3_supported(F * nsq, n->s3_np)) {
-            // Linear [P, F·nsq] → split bf16 fragments, k = sq·F + c (the order of the activations)
-            const size_t K = (size_t)F * nsq;
-            const int NP = n->s3_np, CB = FC_S3_COLS;
-            auto w = find(n, "policy.weight", (size_t)P * K, err);
-            auto bsrc = w ? find(n, "policy.bias", P, err) : nullptr;
-            if (!bsrc) return fail(TG_ERR_WEIGHTS, err);
-            std::vector<uint16_t> ws((size_t)(K / 32) * NP * 64, 0);
-            for (int o = 0; o < P; o++)
-                for (size_t k = 0; k < K; k++) {
-                    int sq = (int)(k / F), c = (int)(k % F);
-                    float v = (*w)[(size_t)o * K + (size_t)c * nsq + sq];
-                    uint16_t hi = f32_to_bf16(v), lo = f32_to_bf16(v - bf16_to_f32(hi));
-                    // [chunk][column block][q][hi|lo][column][8 bf16]: the LDS plane layout of k_fc_s3b
-                    const size_t cb = (size_t)o / CB, col = (size_t)o % CB, q = (k & 31) >> 3;
-                    size_t slot = ((((k >> 5) * (size_t)(NP / CB) + cb) * 4 + q) * 2) * CB + col;
-                    ws[slot * 8 + (k & 7)] = hi;
-                    ws[(slot + CB) * 8 + (k & 7)] = lo;
-                }
-            if (n->value_in_fc && NP > P) {  // column P = the value head, split like every other column
-                auto wv = find(n, "value.weight", K, err);
-                if (!wv) return fail(TG_ERR_WEIGHTS, err);
-                for (size_t k = 0; k < K; k++) {
-                    int sq = (int)(k / F), c = (int)(k % F);
-                    float v = (*wv)[(size_t)c * nsq + sq];
-                    uint16_t hi = f32_to_bf16(v), lo = f32_to_bf16(v - bf16_to_f32(hi));
-                    const size_t cb = (size_t)P / CB, col = (size_t)P % CB, q = (k & 31) >> 3;
-                    size_t slot = ((((k >> 5) * (size_t)(NP / CB) + cb) * 4 + q) * 2) * CB + col;
-                    ws[slot * 8 + (k & 7)] = hi;
-                    ws[(slot + CB) * 8 + (k & 7)] = lo;
-                }
-            }
-            TG_HIP(n->s3_fc.ensure(ws.size() * 2));
-            TG_HIP(hipMemcpy(n->s3_fc.p, ws.data(), ws.size() * 2, hipMemcpyHostToDevice));
-            // the ring kernel's copy: [chunk][tile][hi|lo][lane = q·16 + column within the tile][8 bf16]: a (chunk, tile, half) block
-            // is one KB in the reader's lane order = one LDS-DMA instruction
-            n->s3_fc_ring_on = false;
+        if (split_fc) {
+            TG_HIP(upload(n->s3_fc, pack_fc_s3(fc, np3, FC_S3_COLS)));
             if (P + 1 <= FC_TILES * 16 && K % 64 == 0) {
-                std::vector<uint16_t> wr((size_t)(K / 32) * FC_TILES * 2 * 64 * 8, 0);
-                auto put = [&](size_t o, size_t k, float v) {
-                    uint16_t hi = f32_to_bf16(v), lo = f32_to_bf16(v - bf16_to_f32(hi));
-                    const size_t lane = ((k & 31) >> 3) * 16 + (o & 15);
-                    const size_t slot = (((k >> 5) * FC_TILES + (o >> 4)) * 2) * 64 + lane;
-                    wr[slot * 8 + (k & 7)] = hi;
-                    wr[(slot + 64) * 8 + (k & 7)] = lo;
-                };
-                for (int o = 0; o < P; o++)
-                    for (size_t k = 0; k < K; k++) put((size_t)o, k, (*w)[(size_t)o * K + (size_t)(k % F) * nsq + k / F]);
-                if (n->value_in_fc && NP > P) {
-                    auto wv = find(n, "value.weight", K, err);
-                    if (!wv) return fail(TG_ERR_WEIGHTS, err);
-                    for (size_t k = 0; k < K; k++) put((size_t)P, k, (*wv)[(size_t)(k % F) * nsq + k / F]);
-                }
-                TG_HIP(n->s3_fc_ring.ensure(wr.size() * 2));
-                TG_HIP(hipMemcpy(n->s3_fc_ring.p, wr.data(), wr.size() * 2, hipMemcpyHostToDevice));
-                n->s3_fc_ring_on = true;
+                TG_HIP(upload(n->s3_fc_ring, pack_fc_s3_ring(fc, FC_TILES)));
+                H.w_ring = n->s3_fc_ring.p;
             }
-            std::vector<float> bp(NP, 0.0f);
-            std::copy(bsrc->begin(), bsrc->end(), bp.begin());
-            if (n->value_in_fc && NP > P) bp[P] = n->value_b;
-            else n->value_in_fc = false;
-            TG_HIP(n->s3_fc_b.ensure(bp.size() * 4));
-            TG_HIP(hipMemcpy(n->s3_fc_b.p, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
-            n->s3_fc_on = true;
+            TG_HIP(upload(n->s3_fc_b, fc.bias(np3)));
         }
+        n->s3 = true;
     }
+    // head plan
+    H.kind = !fc_head ? HEAD_CONV_F32 : split_fc ? HEAD_FC_SPLIT : HEAD_FC_F32;
+    H.split_act = split_fc || H.conv_in_tower;
+    H.frag_act = H.kind == HEAD_FC_F32 && !s3 && n->fused && n->tower.frag_out;
+    H.ld = !fc_head ? nsq * n->policy_conv.cout_pad : split_fc ? np3 : np;
+    H.value_col = value_col;
+    H.search_logits = value_col && P <= 2048 && !(s3 && !split_fc);  // (split tower with the f32 FC: keep the plain path)
+    // the FC emits the softmax statistics per column block, nobody re-reads whole rows (one statistics geometry — softmax.cuh — on
+    // both precisions: the split-bf16 FC's ring kernel emits it from its epilogue, k_fc_stats computes it behind k_fc_s3b for ≤ 512 rows)
+    H.stats = value_col && !env_on("TG_NO_FC_STATS") && P + 1 <= FC_TILES * 16 &&
+              (split_fc ? np3 >= FC_TILES * 16 : fc_stats_supported(nsq * F, np, np));
+    H.stat_blocks = H.stats ? FC_STAT_BLOCKS : 0;
+    H.stat_stride = H.stats ? FC_STAT_STRIDE : 0;
+    if (H.kind == HEAD_FC_SPLIT) { H.w = n->s3_fc.p; H.b = n->s3_fc_b.as<float>(); }
+    if (H.kind == HEAD_FC_F32) { H.w = n->policy_w.p; H.b = n->policy_b.as<float>(); H.w_ring = n->policy_w_lin.p; }
+    n->head = H;
+    // activation buffers
     size_t mb = (size_t)e->cfg.max_batch;
     TG_HIP(n->x.ensure(((mb + 15) / 16 * 16) * nsq * F * 4));  // (whole tiles of 16 positions: fragment-major FC input)
     TG_HIP(n->y.ensure(mb * nsq * F * 4));
-    size_t logit_row = e->cfg.policy_head == TG_HEAD_CONV ? (size_t)nsq * n->policy_conv.cout_pad : (size_t)std::max(n->policy_np, n->s3_np);
-    TG_HIP(n->logits.ensure(mb * logit_row * 4));
+    TG_HIP(n->logits.ensure(mb * (size_t)std::max(H.ld, np) * 4));
     TG_HIP(n->planes_nhwc.ensure(mb * nsq * n->cin_pad * 4));
-    // f32 FC head with the value column: the FC emits the softmax statistics per column block, nobody re-reads whole rows
-    const bool s3fc = n->s3 && n->s3_fc_on;
-    // (one statistics geometry — softmax.cuh — on both precisions since round 4: the split-bf16 FC's ring kernel emits it from its
-    // epilogue, k_fc_stats computes it behind k_fc_s3b for ≤ 512 rows)
-    n->fc_stats_on = e->cfg.policy_head == TG_HEAD_FC5 && n->value_in_fc && !env_on("TG_NO_FC_STATS") && e->policy_size + 1 <= FC_TILES * 16 &&
-                     (s3fc ? n->s3_np >= FC_TILES * 16 : fc_stats_supported(nsq * F, n->policy_np, n->policy_np));
-    n->fc_stat_blocks = n->fc_stats_on ? FC_STAT_BLOCKS : 0;
-    n->fc_stat_stride = n->fc_stats_on ? FC_STAT_STRIDE : 0;
-    if (n->fc_stats_on) TG_HIP(n->fc_stats.ensure(mb * (size_t)n->fc_stat_stride * 2 * 4));
+    if (H.stats) TG_HIP(n->fc_stats.ensure(mb * (size_t)H.stat_stride * 2 * 4));
     if (int rc = symm_tables_build(e); rc) return rc;  // once per engine: the policy permutation tables of the 8 symmetries
     n->ready = true;
     return TG_OK;
@@ -548,21 +331,17 @@ bool net_takes_states(const TgEngine* e) { return net_ready(e) && (e->net->fused
 // FC head with the value column: the logits buffer ([max_batch][*ld], logit P = value pre-activation) the search reads when it
 // passes d_policy = nullptr to the forward (no softmax kernel, no probabilities in HBM); nullptr for every other topology
 const float* net_fc_logits(const TgEngine* e, int* ld) {
-    if (!net_ready(e)) return nullptr;
-    const Net* n = e->net;
-    if (e->cfg.policy_head != TG_HEAD_FC5 || !n->value_in_fc || e->policy_size > 2048) return nullptr;
-    if (n->s3 && !n->s3_fc_on) return nullptr;  // split tower with the f32 FC: keep the plain path
-    *ld = n->s3 && n->s3_fc_on ? n->s3_np : n->policy_np;  // the row stride the FC kernel in use writes
-    return n->logits.as<float>();
+    if (!net_ready(e) || !e->net->head.search_logits) return nullptr;
+    *ld = e->net->head.ld;  // the row stride the FC kernel in use writes
+    return e->net->logits.as<float>();
 }
 
 // the block statistics that go with net_fc_logits' buffer ([max_batch][*blocks][2]), or nullptr: the consumer then takes max and
 // Σexp over the whole row itself (softmax_stats_wave)
 const float* net_fc_stats(const TgEngine* e, int* blocks, int* stride) {
-    if (!net_ready(e) || !e->net->fc_stats_on) return nullptr;
-    if (e->net->s3 && !e->net->s3_fc_on) return nullptr;  // split tower with the f32 FC: net_fc_logits declines too
-    *blocks = e->net->fc_stat_blocks;
-    *stride = e->net->fc_stat_stride;
+    if (!net_ready(e) || !e->net->head.stats || !e->net->head.search_logits) return nullptr;  // (as net_fc_logits declines)
+    *blocks = e->net->head.stat_blocks;
+    *stride = e->net->head.stat_stride;
     return e->net->fc_stats.as<float>();
 }
 
@@ -572,11 +351,11 @@ const float* net_fc_stats(const TgEngine* e, int* blocks, int* stride) {
 // the search whether the next such forward will do so (then its backup reads child_logit, else the logits buffer).
 bool net_gather_ok(const TgEngine* e, int leaves) {
     if (!net_ready(e)) return false;
-    const Net* n = e->net;
+    const HeadPlan& H = e->net->head;
     static const bool off = env_on("TG_NO_FC_GATHER");  // A/B: logits rows + the backup's own gather (same bits)
-    if (off || e->cfg.policy_head != TG_HEAD_FC5 || !n->fc_stats_on || !n->value_in_fc) return false;
-    if (n->s3) return n->s3_fc_on && n->s3_fc_ring_on && !env_on("TG_S3_NO_FC_RING") && fc_s3_ring_supported(leaves, e->g.nsq * n->F, e->policy_size + 1);
-    return fc_gather_supported(leaves, e->g.nsq * n->F, n->policy_np);
+    if (off || !H.stats || !H.search_logits) return false;
+    if (H.kind == HEAD_FC_SPLIT) return H.w_ring && !env_on("TG_S3_NO_FC_RING") && fc_s3_ring_supported(leaves, e->g.nsq * e->net->F, e->policy_size + 1);
+    return fc_gather_supported(leaves, e->g.nsq * e->net->F, H.ld);
 }
 void net_set_gather(TgEngine* e, const FcGatherArgs* g) {
     if (!e || !e->net) return;
@@ -599,6 +378,7 @@ static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const ui
     if (nb <= 0) return TG_OK;
     if (nb > e->cfg.max_batch) return fail(TG_ERR_INVALID_ARG, "batch larger than max_batch");
     Net* n = e->net;
+    const HeadPlan& H = n->head;
     hipStream_t st = e->stream;
     const int F = n->F, nsq = e->g.nsq, N = e->g.n;
     const int M = nb * nsq;
@@ -628,11 +408,10 @@ static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const ui
     }
     if (n->s3) {
         if (chain) chain->push_back(prof_event(n, st));
-        const bool split_out = n->s3_fc_on || n->s3_head_on;
         TowerS3Params T3 = n->tower_s3;
-        if (n->s3_head_on) T3.head_out = n->logits.as<float>();
-        if (d_states) TG_HIP(launch_tower_s3_states(st, d_states, T3, x, nb, N, split_out));
-        else TG_HIP(launch_tower_s3(st, d_planes, T3, x, nb, N, split_out));
+        if (H.conv_in_tower) T3.head_out = n->logits.as<float>();
+        if (d_states) TG_HIP(launch_tower_s3_states(st, d_states, T3, x, nb, N, H.split_act));
+        else TG_HIP(launch_tower_s3(st, d_planes, T3, x, nb, N, H.split_act));
         if (chain) chain->push_back(prof_event(n, st));
     } else if (n->fused) {
         if (chain) chain->push_back(prof_event(n, st));
@@ -654,36 +433,32 @@ static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const ui
         }
     }
     float* logits = n->logits.as<float>();
+    const int P = e->policy_size;
     bool value_done = false;
-    if (e->cfg.policy_head == TG_HEAD_CONV) {
+    if (H.kind == HEAD_CONV_F32) {
         const ConvLayer& L = n->policy_conv;
-        if (!(n->s3 && n->s3_head_on))
+        if (!H.conv_in_tower)
             TG_HIP(launch_conv3x3(st, x, L.w.as<float>(), L.b.as<float>(), nullptr, logits, M, N, F, L.cout_pad, L.cout_pad, L.cout, false));
         // (exact-f32 path: the softmax's launch computes the value head too — one launch less per forward)
         const ValueHeadArgs vh{x, n->value_w.as<float>(), n->value_b, nsq * F, d_eval};
-        const bool plain_value = !(n->s3 && (n->s3_fc_on || n->s3_head_on));
-        TG_HIP(launch_softmax(st, logits, nsq * L.cout_pad, true, nsq, L.cout_pad, e->policy_size, nb, d_policy, nullptr, plain_value ? &vh : nullptr, &value_done));
-    } else if (n->s3 && n->s3_fc_on) {
-        float* stats = n->fc_stats_on ? n->fc_stats.as<float>() : nullptr;
-        const bool gather = !d_policy && n->gather_on && net_gather_ok(e, nb);
-        TG_HIP(launch_fc_s3(st, x, n->s3_fc.p, n->s3_fc_ring_on ? n->s3_fc_ring.p : nullptr, n->s3_fc_b.as<float>(), logits, nb, nsq * F, n->s3_np, n->s3_np,
-                            e->policy_size + (n->value_in_fc ? 1 : 0), stats, e->policy_size, gather ? &n->gather : nullptr));
-        if (d_policy && stats) TG_HIP(launch_softmax_stats(st, logits, n->s3_np, stats, n->fc_stat_blocks, n->fc_stat_stride, e->policy_size, nb, d_policy, d_eval));
-        else if (d_policy) TG_HIP(launch_softmax(st, logits, n->s3_np, false, nsq, 0, e->policy_size, nb, d_policy, n->value_in_fc ? d_eval : nullptr));
+        TG_HIP(launch_softmax(st, logits, H.ld, true, nsq, L.cout_pad, P, nb, d_policy, nullptr, H.split_act ? nullptr : &vh, &value_done));
     } else {
-        float* stats = n->fc_stats_on ? n->fc_stats.as<float>() : nullptr;
-        const bool gather = !d_policy && n->gather_on && net_gather_ok(e, nb);
-        static const bool lin_src = !env_on("TG_FC_PERMUTED_SRC");  // A/B: the ring's LDS-DMA reads the [chunk][column][q] layout (same bits)
-        TG_HIP(launch_gemm(st, x, nsq * F, n->policy_w.as<float>(), n->policy_b.as<float>(), logits, nb, nsq * F, n->policy_np,
-                           n->policy_np, e->policy_size + (n->value_in_fc ? 1 : 0), !n->s3 && n->fused && n->tower.frag_out,
-                           stats, e->policy_size, gather ? &n->gather : nullptr, lin_src ? n->policy_w_lin.as<float>() : nullptr));
-        if (d_policy && stats) TG_HIP(launch_softmax_stats(st, logits, n->policy_np, stats, n->fc_stat_blocks, n->fc_stat_stride, e->policy_size, nb, d_policy, d_eval));
-        else if (d_policy) TG_HIP(launch_softmax(st, logits, n->policy_np, false, nsq, 0, e->policy_size, nb, d_policy, n->value_in_fc ? d_eval : nullptr));
+        float* stats = H.stats ? n->fc_stats.as<float>() : nullptr;
+        const FcGatherArgs* gather = !d_policy && n->gather_on && net_gather_ok(e, nb) ? &n->gather : nullptr;
+        const int cols = P + (H.value_col ? 1 : 0);
+        if (H.kind == HEAD_FC_SPLIT) TG_HIP(launch_fc_s3(st, x, H.w, H.w_ring, H.b, logits, nb, nsq * F, H.ld, H.ld, cols, stats, P, gather));
+        else {
+            static const bool lin_src = !env_on("TG_FC_PERMUTED_SRC");  // A/B: the ring's LDS-DMA reads the [chunk][column][q] layout (same bits)
+            TG_HIP(launch_gemm(st, x, nsq * F, (const float*)H.w, H.b, logits, nb, nsq * F, H.ld, H.ld, cols, H.frag_act, stats, P, gather,
+                               lin_src ? (const float*)H.w_ring : nullptr));
+        }
+        if (d_policy && stats) TG_HIP(launch_softmax_stats(st, logits, H.ld, stats, H.stat_blocks, H.stat_stride, P, nb, d_policy, d_eval));
+        else if (d_policy) TG_HIP(launch_softmax(st, logits, H.ld, false, nsq, 0, P, nb, d_policy, H.value_col ? d_eval : nullptr));
     }
-    if (!d_policy && !(e->cfg.policy_head == TG_HEAD_FC5 && n->value_in_fc)) return fail(TG_ERR_STATE, "logits-only forward needs the FC head with the value column");
-    if (e->cfg.policy_head == TG_HEAD_FC5 && n->value_in_fc) {
+    if (!d_policy && !H.value_col) return fail(TG_ERR_STATE, "logits-only forward needs the FC head with the value column");
+    if (H.value_col) {
         // eval = tanh(logit P), written by the softmax kernel (or taken by the tree backup straight from the logits)
-    } else if (n->s3 && (n->s3_fc_on || n->s3_head_on)) TG_HIP(launch_value_head_s3(st, x, n->value_w.as<float>(), n->value_b, nb, nsq * F, d_eval));
+    } else if (H.split_act) TG_HIP(launch_value_head_s3(st, x, n->value_w.as<float>(), n->value_b, nb, nsq * F, d_eval));
     else if (!value_done) TG_HIP(launch_value_head(st, x, n->value_w.as<float>(), n->value_b, nb, nsq * F, d_eval));
     if (chain) chain->push_back(prof_event(n, st));
     return TG_OK;
@@ -920,13 +695,10 @@ int tg_eval_examples(TgEngine* e, int n, const void* states, const int32_t* n_mo
     const float* fc_logits = net_fc_logits(e, &ld);
     EvalLogits L;
     if (fc_logits) L = EvalLogits{fc_logits, (size_t)ld, 1, ld, P, nullptr};  // logits-only forward: v = tanh(logit P), as k_softmax_stats takes it
-    else if (e->cfg.policy_head == TG_HEAD_CONV) {
+    else if (net->head.kind == HEAD_CONV_F32) {
         const int cs = net->policy_conv.cout_pad;
         L = EvalLogits{net->logits.as<float>(), (size_t)nsq * cs, nsq, cs, P / nsq, e->s_eval.as<float>()};
-    } else {
-        const int stride = net->s3 && net->s3_fc_on ? net->s3_np : net->policy_np;
-        L = EvalLogits{net->logits.as<float>(), (size_t)stride, 1, stride, P, e->s_eval.as<float>()};
-    }
+    } else L = EvalLogits{net->logits.as<float>(), (size_t)net->head.ld, 1, net->head.ld, P, e->s_eval.as<float>()};
     std::vector<int4> h_rec;
     std::vector<uint16_t> h_moves;
     std::vector<uint32_t> h_visits;

@@ -19,6 +19,7 @@
 
 #include "engine.h"
 #include "kernels.h"
+#include "net_pack.h"
 #include "rng.cuh"
 
 namespace tg {
@@ -26,8 +27,6 @@ namespace tg {
 struct Id128 { char bytes[128]; };  // ncclUniqueId
 
 namespace {
-
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 struct ParamInfo {
     std::string name;
@@ -748,7 +747,7 @@ int tg_train_create(TgEngine* e, const TgTrainConfig* cfg) {
         logit_row = (size_t)nsq * c.OP;
     } else {
         const int K = F * nsq;
-        t->NP = (K % 64 == 0) ? round_up(P, 208) : round_up(P, 64);
+        t->NP = fc_padded_cols(K, P);  // the inference FC's padding (net_pack.h)
         t->Pp = round_up(P, 32);
         t->KP = round_up(K, 64);
         if (t->Pp > t->NP) return fail(TG_ERR_INVALID_ARG, "internal: FC padding");
