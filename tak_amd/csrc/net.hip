@@ -186,7 +186,8 @@ int net_finalize(TgEngine* e) {
     const bool s3 = n->precision == TG_PRECISION_BF16X3;
     n->s3 = false;
     if (s3 && (!tower_s3_supported(N, F) || 1 + 2 * R > 48 || n->cin > 96))
-        return fail(TG_ERR_INVALID_ARG, "TG_PRECISION_BF16X3 supports 5x5 with 64 or 128 filters and 6x6 with 128 filters");
+        return fail(TG_ERR_INVALID_ARG, "TG_PRECISION_BF16X3 supports 5x5 with 64 or 128 filters and 6x6 with 128 filters, with at most "
+                                        "48 conv layers (23 residual blocks); this network has " + std::to_string(1 + 2 * R) + " layers");
     // the FC head's geometry: padded outputs on either precision, which FC runs, and whether the padding leaves the value
     // head a column (decided here, once, for every layout below)
     const int np = fc_head ? fc_padded_cols(K, P) : 0, np3 = s3 ? round_up(P, FC_S3_COLS) : 0;

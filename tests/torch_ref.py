@@ -250,12 +250,14 @@ TINY_P = 1e-12
 # b comes from the arithmetic, not from a fit: the FC path's softmax takes exp(x − M) as v_exp_f32((x − M)·log2 e) (softmax.cuh, stat_exp);
 # the rounding of x − M and of the product by log2 e are each ≤ 2⁻²⁴ relative, i.e. ≤ 2⁻²⁴·|x − M| ≤ 2⁻²⁴·|log p| in the natural log:
 # b = 2·log2 e·2⁻²⁴ (≈ 1.7e-7) covers both with the log2 e factor of the base-2 form to spare.
-# a, t and c sit about 3× above the engine's worst error measured on an MI355X over the whole GPU suite (every case check_forward,
-# check_logp or check_priors gates — the trained-like sweep of tests/test_gpu_fp64.py sets every maximum):
+# a, t and c sit 2 – 3× above the engine's worst error measured on an MI355X over the whole GPU suite (every case check_forward,
+# check_logp or check_priors gates — the trained-like sweeps of tests/test_gpu_fp64.py and, for the two f32 maxima at K = 4800 / 6400 of
+# the policy FC, tests/test_gpu_topology_forward.py set every maximum):
 #              worst |Δlog p| − b·|log p64|          worst row TV                  worst |Δv| − 2⁻²³ over (1 − v64²)
-#   f32        6.5e-5 (5×5×128 FC, planes, B=65)     7.3e-6 (5×5×128 FC, B=1300)   9.8e-6 (5×5×128 FC, B=513)
+#   f32        6.5e-5 (5×5×128 FC, planes, B=65)     1.0e-5 (5×5×256 FC, B=2049)   1.1e-5 (5×5×192 FC, B=2049)
 #   bf16x3     3.1e-4 (6×6×128 conv, planes, B=700)  3.9e-5 (6×6×128 conv, B=700)  9.8e-5 (5×5×64 FC, B=2400)
-# (PyTorch's own fp32 forward on the same kind of networks: ≤ 1.3e-5, 2.1e-6, 5.9e-6.)  The teeth test (tests/test_forward_gates.py)
+# (PyTorch's own fp32 forward on the same kind of networks: ≤ 1.3e-5, 2.1e-6, 5.9e-6.  Networks of 49 layers are gated at these constants
+# times the reference's own depth growth, depth_scaled_gates: the engine's worst there 3.5e-5, 4.8e-6, 1.2e-5 under ratios of 2 – 6.)  The teeth test (tests/test_forward_gates.py)
 # rejects each of its mutations under both sets; the smallest of them, a value bias off by 1e-3, is 1e-3 of pre-activation error.
 _B_EXP = 2.0 * 1.4426950408889634 * 2.0 ** -24
 GATES = {
@@ -336,10 +338,7 @@ def _assert_policy(m, g, what):
     assert m["tv"] <= g["t"], f"{what}: row total variation {m['tv']:.3e} > t = {g['t']:.1e}"
 
 
-def check_forward(p, v, ref, precision, what="forward"):
-    """The forward gates of `precision` (GATES) on an engine's (or any) probabilities p [B, P] and values v [B] against forward64's `ref`
-    (the same rows).  Asserts, naming `what` and the gate that failed; returns the measured metrics."""
-    g = GATES[precision]
+def _forward_metrics(p, v, ref, g, what):
     p = np.asarray(p)
     assert p.shape == ref["logp"].shape and np.shape(v) == ref["v"].shape, (what, p.shape, ref["logp"].shape)
     m = _policy_metrics(p, ref["logp"], g)
@@ -348,6 +347,37 @@ def check_forward(p, v, ref, precision, what="forward"):
     pre = np.maximum(dv - 2.0 ** -23, 0.0) / np.maximum(slope, 1e-300)
     m.update(v_abs=float(dv.max()) if dv.size else 0.0, pre=float(pre.max()) if pre.size else 0.0,
              v_max=float(np.abs(ref["v"]).max()) if dv.size else 0.0, rows=int(p.shape[0]))
+    return m, dv, slope
+
+
+def measure_forward(p, v, ref, what="forward"):
+    """check_forward's metrics (logp_a, tv, pre, …) of p, v against forward64's `ref`, with nothing asserted: what a gate that has to
+    follow the reference's own error is derived from (depth_scaled_gates)"""
+    return _forward_metrics(p, v, ref, GATES["f32"], what)[0]
+
+
+def depth_scaled_gates(net, shallow, planes, ref, ref_shallow, precision="f32"):
+    """GATES[precision] for a network far deeper than the 5-layer ones its constants were set on.  Rounding error grows with depth; how
+    much is read off the REFERENCE, not off the engine: PyTorch fp32's own distance to float64 on `net` over that on `shallow` (the
+    same shape with 2 blocks), on the same `planes`, metric by metric.  a, t and c are multiplied by max(1, ratio of logp_a, tv, pre);
+    b (the exp's argument rounding) does not depend on depth.  → (gates, ratios, PyTorch fp32's metrics on net, on shallow)"""
+    deep = measure_forward(*forward(net, planes), ref, "PyTorch fp32, deep")
+    flat = measure_forward(*forward(shallow, planes), ref_shallow, "PyTorch fp32, 2 blocks")
+    ratios = {k: deep[k] / flat[k] for k in ("logp_a", "tv", "pre")}
+    g = dict(GATES[precision])
+    for const, metric in (("a", "logp_a"), ("t", "tv"), ("c", "pre")):
+        g[const] *= max(1.0, ratios[metric])
+    return g, ratios, deep, flat
+
+
+def check_forward(p, v, ref, precision, what="forward", gates=None):
+    """The forward gates of `precision` (GATES) on an engine's (or any) probabilities p [B, P] and values v [B] against forward64's `ref`
+    (the same rows).  Asserts, naming `what` and the gate that failed; returns the measured metrics.
+    gates: constants in GATES' form that take the place of GATES[precision] (depth_scaled_gates: networks far deeper than the ones
+    the constants were set on)."""
+    g = GATES[precision] if gates is None else gates
+    p = np.asarray(p)
+    m, dv, slope = _forward_metrics(p, v, ref, g, what)
     _assert_policy(m, g, what)
     assert (dv <= g["c"] * slope + 2.0 ** -23).all(), (f"{what}: |v − v64| beyond c·(1 − v64²) + 2⁻²³ "
                                                        f"(implied pre-tanh error {m['pre']:.3e} > c = {g['c']:.1e})")
