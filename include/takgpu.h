@@ -975,8 +975,9 @@ typedef struct TgProfile {
     int64_t conv_flops;       /* algorithmic FLOPs of one timed launch: 2·M·9·F·F (per-layer path) or, for the fused
                                  tower, 2·M·9·(C_in·F + 2R·F·F) — every input plane counted as data                */
     int64_t conv_flops_executed; /* FLOPs of the MFMAs the timed launch issues: less than conv_flops when the fused tower
-                                 takes the per-position constant input planes (reserves, colour, fcd) as a bias and runs
-                                 layer 0 over the board planes only — price the MFMA pipe against THIS figure       */
+                                 takes the per-position constant input planes (reserves, colour, fcd) as a bias and sums
+                                 layer 0 from the set board planes' weight rows, without an MFMA — price the MFMA pipe
+                                 against THIS figure                                                                */
 } TgProfile;
 TG_API int tg_profile_enable(TgEngine* e, int sample_every); /* 0 disables */
 /* Board-path micro-benchmark: uploads n states + one legal move each, then runs `reps`

@@ -25,7 +25,7 @@ int main(int argc, char** argv) {
         T.w[l] = w; T.b[l] = b;
     }
     float* S; hipMalloc(&S, (size_t)64 * 9 * F * 4); hipMemset(S, 0, (size_t)64 * 9 * F * 4);
-    T.cb = 1; T.cb_cin_pad = 32; T.cb_last_t = 3; T.w0_board = T.w[0]; T.cplane_sums = S;
+    T.cb = 1; T.w0_rows = T.w[0]; T.cplane_sums = S;  // (layer 0's rows: any 29·9·F floats do for a timing)
     unsigned* ctl; hipMalloc(&ctl, TOWER_SPLIT_CTL_WORDS * 4); hipMemset(ctl, 0, TOWER_SPLIT_CTL_WORDS * 4);
     T.split_flags = ctl; T.split_err = (int*)ctl + TOWER_SPLIT_CTL_WORDS - 32;
     float *out, *scratch; hipMalloc(&out, (size_t)(B + 16) * nsq * F * 4); hipMalloc(&scratch, (size_t)2 * TOWER_SPLIT_MAX_BATCH * nsq * F * 4);

@@ -26,17 +26,17 @@ int main(int argc, char** argv) {
         T.w[l] = w; T.b[l] = b;
     }
     float* S; hipMalloc(&S, (size_t)46 * 9 * F * 4); hipMemset(S, 0, (size_t)46 * 9 * F * 4);
-    T.cb = 1; T.cb_cin_pad = 32; T.cb_last_t = 3; T.w0_board = T.w[0]; T.cplane_sums = S;
+    T.cb = 1; T.w0_rows = T.w[0]; T.cplane_sums = S;  // (layer 0's rows: any 29·9·F floats do for a timing)
     float* out; hipMalloc(&out, (size_t)(B + 16) * 25 * F * 4);
     unsigned long long* stamps; hipMalloc(&stamps, (size_t)nl * 16 * 8 * 8); hipMemset(stamps, 0, (size_t)nl * 16 * 8 * 8);
     hipMemcpyToSymbol(HIP_SYMBOL(g_tower_stamps), &stamps, sizeof(stamps));
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     auto launch = [&]() {
-        if (pw == 1) return launch_tower_t<2, 4, 2, 4, true, true>(nullptr, (const float*)states, T, out, B, n, 1, 4);
-        if (pw == 2) return launch_tower_t<4, 4, 2, 4, true, true>(nullptr, (const float*)states, T, out, B, n, 2, 4);
-        if (pw == 4) return launch_tower_t<7, 4, 2, 4, true, true>(nullptr, (const float*)states, T, out, B, n, 4, 4);
-        if (pw == 8) return launch_tower_t<13, 4, 2, 4, true, true>(nullptr, (const float*)states, T, out, B, n, 8, 4);
-        return launch_tower_t<13, 8, 2, 4, true, true>(nullptr, (const float*)states, T, out, B, n, 16, 4);
+        if (pw == 1) return launch_tower_t<2, 4, 0, 4, true, true, 5>(nullptr, (const float*)states, T, out, B, n, 1, 4);
+        if (pw == 2) return launch_tower_t<4, 4, 0, 4, true, true, 5>(nullptr, (const float*)states, T, out, B, n, 2, 4);
+        if (pw == 4) return launch_tower_t<7, 4, 0, 4, true, true, 5>(nullptr, (const float*)states, T, out, B, n, 4, 4);
+        if (pw == 8) return launch_tower_t<13, 4, 0, 4, true, true, 5>(nullptr, (const float*)states, T, out, B, n, 8, 4);
+        return launch_tower_t<13, 8, 0, 4, true, true, 5>(nullptr, (const float*)states, T, out, B, n, 16, 4);
     };
     for (int i = 0; i < 3; i++) launch();
     hipDeviceSynchronize();

@@ -34,21 +34,21 @@ int main(int argc, char** argv) {
     tower_halo_slotmap(5, c5 ? 8 : 16, c5 ? 37 : 36, map.data());
     uint32_t* dmap; hipMalloc(&dmap, map.size() * 4); hipMemcpy(dmap, map.data(), map.size() * 4, hipMemcpyHostToDevice);
     T.slotmap = dmap; T.halo_pw = c5 ? 8 : 16; T.halo_ps = c5 ? 37 : 36;
-    // variant 82: the halo tower with the constant input planes as a per-position bias (TowerParams.cb): layer 0 over 32 channels
-    // variant 83: the square-tile tower k_tower_sq<2, true, true> with the same parameters
+    // variant 82: the halo tower with the constant input planes as a per-position bias (TowerParams.cb): layer 0 as a sum of weight rows
+    // variant 83: the square-tile tower k_tower_sq<0, true, true> with the same parameters
     if (variant == 82 || variant == 83 || c5) {
-        size_t wf = (size_t)9 * 32 * F;
+        size_t wf = (size_t)27 * 9 * F;  // R[26 board planes + the −0.0f block][tap][F]
         float* w; hipMalloc(&w, wf * 4);
-        std::vector<float> hw(wf);
-        for (size_t i = 0; i < wf; i++) hw[i] = 0.01f * (float)((i * 2654435761u) % 97) - 0.45f;
+        std::vector<float> hw(wf, -0.0f);
+        for (size_t i = 0; i < (size_t)26 * 9 * F; i++) hw[i] = 0.01f * (float)((i * 2654435761u) % 97) - 0.45f;
         hipMemcpy(w, hw.data(), wf * 4, hipMemcpyHostToDevice);
         float* S; hipMalloc(&S, (size_t)46 * 9 * F * 4); hipMemset(S, 0, (size_t)46 * 9 * F * 4);
-        T.cb = 1; T.cb_cin_pad = 32; T.cb_last_t = 3; T.w0_board = w; T.cplane_sums = S;
+        T.cb = 1; T.w0_rows = w; T.cplane_sums = S;
     }
     auto launch = [&]() {
-        if (c5) return launch_tower_halo_t<13, 8, 2, 8, 5, true, true>(nullptr, (const float*)states, T, out, B, 8);
-        if (variant == 83) return launch_tower_sq_t<2, true, true>(nullptr, (const float*)states, T, out, B);
-        if (variant == 82) return launch_tower_halo_t<13, 8, 2, 4, 5, true, true>(nullptr, (const float*)states, T, out, B, 4);
+        if (c5) return launch_tower_halo_t<13, 8, 0, 8, 5, true, true>(nullptr, (const float*)states, T, out, B, 8);
+        if (variant == 83) return launch_tower_sq_t<0, true, true>(nullptr, (const float*)states, T, out, B);
+        if (variant == 82) return launch_tower_halo_t<13, 8, 0, 4, 5, true, true>(nullptr, (const float*)states, T, out, B, 4);
         if (variant == 80) return launch_tower_halo_t<13, 8, 5, 4, 5, true>(nullptr, (const float*)states, T, out, B, 4);
         if (variant == 16) return launch_tower_t<7, 16, 5, 4, true>(nullptr, (const float*)states, T, out, B, n, 16, 4);
         if (variant == 4) return launch_tower_t<25, 4, 5, 4, true>(nullptr, (const float*)states, T, out, B, n, 16, 4);

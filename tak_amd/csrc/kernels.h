@@ -90,15 +90,15 @@ struct TowerParams {
     // board_channels(n) = 26 / 28 vary over the board; the reserves one-hots, the colour plane and the fcd plane (46 of 72 on
     // 5×5, 64 of 92 on 6×6; alpha-tak/src/repr/reserves.rs:4-28, repr/game.rs:28-50) hold ONE value per position.  Their
     // 3×3 convolution is therefore a per-position bias that depends only on which taps of a square stay on the board — 9
-    // border classes — and layer 0 runs its MFMAs over the board planes alone (K = 9·32 instead of 9·80 / 9·96):
-    //   w0_board      conv0 restricted to the board planes, Wp[9·32/16][CoutP][16], last chunk permuted (cb_last_t)
+    // border classes: PB = bias + Σ_{planes set} S + fcd · S[fcd plane] (in that order).  The board planes hold 0 or 1 and a
+    // position sets few of them (at most one bit per stone), so layer 0 issues no MFMA at all: a square's output is PB plus the
+    // weight rows of its neighbours' set planes, summed in the order tower_stage.cuh (tower_cb_layer0) fixes.
     //   cplane_sums   S[plane − board_channels][class][F] = Σ over the taps valid in that class of the folded conv0 weight
-    // and the kernel adds bias + Σ_{planes set} S + fcd · S[fcd plane] (in that order) in the epilogue of layer 0.
+    //   w0_rows       R[plane ≤ board_channels][tap][F]: the folded conv0 weights of the board planes, then a block of −0.0f
+    //                 (net_pack.h pack_board_rows)
     int cb;
-    int cb_cin_pad;       // 32
-    int cb_last_t;        // 3: ten / twelve real channels in the last 16-channel chunk
-    const float* w0_board;
     const float* cplane_sums;
+    const float* w0_rows;
     // k_tower_split (small batches of 128-filter networks): one counter per position of a launch (zero between launches) and an
     // error word a bounded wait raises; nullptr: the split path is not used
     unsigned* split_flags;

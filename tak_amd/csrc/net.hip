@@ -59,7 +59,7 @@ struct Net {
     bool fused = false;  // whole tower in one launch (k_tower)
     TowerParams tower;
     ConvLayer conv0_tower;             // conv0 with the last input chunk permuted (layer 0 of the fused towers)
-    ConvLayer conv0_board;             // conv0 over the board planes only (TowerParams.cb)
+    DevBuf board_rows;                 // R[board plane, −0.0f block][tap][F]: layer 0 as a sum of rows (TowerParams.cb)
     DevBuf cplane_sums;                // S[constant plane][border class][F] (TowerParams.cb)
     int64_t conv_flops_exec = 0;       // MFMA FLOPs the timed launch actually issues (≤ conv_flops when constant planes are a bias)
     DevBuf halo_map;                   // tile slot → square table of the halo tower (k_tower_halo)
@@ -222,13 +222,14 @@ int net_finalize(TgEngine* e) {
         if (T.cin_last_t < 2) T.cin_last_t = 4;
         TG_HIP(upload_conv(f0, F, n->cin, n->cin_pad, n->conv0_tower, T.cin_last_t));
         T.w[0] = n->conv0_tower.w.as<float>(); T.b[0] = n->conv0.b.as<float>();
-        // Constant planes as a bias (kernels.h TowerParams.cb; states entry): conv0 over the board planes, and the table S
-        T.cb = 0; T.cb_cin_pad = 32; T.cb_last_t = 3; T.w0_board = nullptr; T.cplane_sums = nullptr;
+        // Constant planes as a bias (kernels.h TowerParams.cb; states entry): the table S, and conv0's weights of the board planes
+        // as the rows layer 0 sums
+        T.cb = 0; T.cplane_sums = nullptr; T.w0_rows = nullptr;
         const int bc = board_channels(N), nconst = n->cin - bc;
         if (!env_on("TG_NO_CONST_BIAS") && bc > 16 && bc <= 28 && nconst > 0) {
-            TG_HIP(upload_conv(restrict_to_board(f0, F, n->cin, bc), F, bc, T.cb_cin_pad, n->conv0_board, T.cb_last_t));
             TG_HIP(upload(n->cplane_sums, pack_cplane_sums(f0, F, n->cin, bc)));
-            T.cb = 1; T.w0_board = n->conv0_board.w.as<float>(); T.cplane_sums = n->cplane_sums.as<float>();
+            TG_HIP(upload(n->board_rows, pack_board_rows(f0, F, n->cin, bc)));
+            T.cb = 1; T.cplane_sums = n->cplane_sums.as<float>(); T.w0_rows = n->board_rows.as<float>();
         }
         for (int i = 0; i < R; i++) {
             T.w[1 + 2 * i] = n->res1[i].w.as<float>(); T.b[1 + 2 * i] = n->res1[i].b.as<float>();
@@ -396,14 +397,12 @@ static int net_forward_impl(TgEngine* e, int nb, const float* d_planes, const ui
         n->conv_rows = M;
         // algorithmic FLOPs of one timed launch: one F→F conv (per-layer path) or the whole tower (fused)
         n->conv_flops = (n->fused || n->s3) ? 2ll * M * 9 * ((long long)n->cin * F + 2ll * n->R * F * F) : 2ll * M * 9 * F * F;
-        // executed: with the constant planes as a bias layer 0 multiplies 16 + 4·cb_last_t input channels per tap, not cin; the
-        // square-tile tower issues the MFMAs of on-board (square, tap) pairs only (169 of 225 on 5×5): in the F → F layers, and in
-        // layer 0 where it runs over the board planes
+        // executed: with the constant planes as a bias layer 0 issues no MFMA (it is a sum of weight rows on the vector pipe); the
+        // square-tile tower issues the MFMAs of on-board (square, tap) pairs only (169 of 225 on 5×5) in the F → F layers
         if (n->fused && !n->s3) {
             const bool cb0 = d_states && n->tower.cb;
-            const long long c0 = cb0 ? 16 + 4 * n->tower.cb_last_t : n->cin;
             const long long taps = tower_square_tiles(N, F, nb) ? (long long)nb * 169 : 9ll * M;  // (row, tap) pairs of a layer ≥ 1
-            n->conv_flops_exec = 2ll * (cb0 ? taps : 9ll * M) * c0 * F + 2ll * taps * 2ll * n->R * F * F;
+            n->conv_flops_exec = (cb0 ? 0ll : 2ll * 9 * M * n->cin * F) + 2ll * taps * 2ll * n->R * F * F;
         } else n->conv_flops_exec = n->conv_flops;
         chain->push_back(prof_event(n, st));
     }

@@ -146,6 +146,18 @@ inline std::vector<float> pack_cplane_sums(const Folded& f0, int O, int I, int b
     return S;
 }
 
+// Layer 0 of the exact states-entry towers as a sum of rows (tower_stage.cuh tower_cb_layer0): R[plane][tap][O] — for the bc
+// board planes the folded conv0 weight of (output channel, plane, tap), channels contiguous, the nine taps of a plane side by
+// side; then one more block R[bc][tap][O] of −0.0f, the row a square without a stone adds: x + (−0.0f) = x, bit for bit, for
+// every x (+0.0f would turn a sum of −0.0f into +0.0f)
+inline std::vector<float> pack_board_rows(const Folded& f0, int O, int I, int bc) {
+    std::vector<float> R((size_t)(bc + 1) * 9 * O, -0.0f);
+    for (int c = 0; c < bc; c++)
+        for (int tap = 0; tap < 9; tap++)
+            for (int o = 0; o < O; o++) R[((size_t)c * 9 + tap) * O + o] = f0.w[((size_t)o * I + c) * 9 + tap];
+    return R;
+}
+
 // element k = sq·F + c (the order of the activations) of a row of Linear [*, F·nsq] over the NCHW flattening c·nsq + sq
 // (net5.rs:86 view)
 inline float nhwc_at(const float* row, int F, int nsq, size_t k) { return row[(k % F) * nsq + k / F]; }

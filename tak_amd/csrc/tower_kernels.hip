@@ -7,9 +7,13 @@
 //   k_tower_halo            the same tower on the HALO image (zero cells between board rows and positions, taps as
 //                           ds_read immediates, conflict-free slot table): full batches, 89 – 94 % of the MFMA peak
 //   k_tower_sq              5×5 with 64 filters at full batches: square tiles (tile = board square, column = position), only
-//                           the MFMAs of on-board taps issued (169 of 225), layer 0 over the board planes included; same bits
+//                           the MFMAs of on-board taps issued (169 of 225); same bits
 // Every variant performs the same products in the same order: a position's outputs are the same bits whatever batch (and
 // therefore kernel) evaluates it (tests/test_gpu_net.py, tests/test_gpu_variants.py).
+// Layer 0 of the states entry (TowerParams.cb) issues no MFMA in any of the four: a board plane holds 0 or 1 and a position sets
+// few of them, so a square's output is the constant-plane bias plus the weight rows of its neighbours' set planes, summed by
+// the one function tower_cb_layer0 (tower_stage.cuh) and stored straight into the image layer 1 reads.  The planes entry
+// (arbitrary input data) and TG_NO_CONST_BIAS keep the dense layer 0.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,33 +38,26 @@ namespace tg {
 // tiles it produces).  Only the input planes are read from HBM and only the final activations are
 // written (for the policy / value heads); per layer the only global traffic is the L2-resident weights.
 // ------------------------------------------------------------------------------------------------
-// ---- constant input planes as a per-position bias (TowerParams.cb; states entry of the fused towers; tower_stage.cuh) ----
-// Stages what layer 0 needs for the positions of one workgroup: the 26 / 28 BOARD planes of every square as a plain image of
-// 32 channels per row (last chunk permuted for cb_last_t = 3), and the table PB[position][border class][F].
-template <int NWAVES>
-__device__ __forceinline__ void tower_stage_states_cb(f32x4* lds4, f32x4* pb4, const uint8_t* states, int pos0, int npos, int n,
-                                                      int LS4, const TowerParams& T) {
+// ---- layer 0 of the states entry (TowerParams.cb; tower_stage.cuh) ----
+// The positions of one workgroup, one wave per position at a time: the wave unpacks the state (lane = square) and sums layer 0's
+// weight rows with its lanes as channels (tower_cb_layer0: the constant planes as the bias PB, the set board planes' rows of
+// TowerParams.w0_rows; F = 128: two passes).  put(p, o, ch, y) receives the output of this lane's channel ch at square o of the
+// workgroup's position p, bias and ReLU applied: every kernel stores it where its layer 1 reads it.
+template <int NWAVES, int NB, int F, class Put>
+__device__ __forceinline__ void tower_stage_layer0(const uint8_t* states, int pos0, int npos, const TowerParams& T, Put&& put) {
+    static_assert(F == 64 || F == 128, "lanes are channels");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const Geom geo = make_geom(n);
-    const int nsq = n * n;
-    // one wave per position at a time, lane = square; a wave's positions are requested two at a time (C2: 16 positions, 8 waves —
-    // one memory round trip instead of two)
+    const Geom geo = make_geom(NB);
     auto stage_one = [&](int p, const WRaw& raw) {
         WState ws;
         ws_unpack(ws, raw, geo);
         const float fcd = fcd_value(ws, geo);
         const RowMask m = ws_row_mask(ws, geo);
-        if (lane < nsq) {
-            f32x4* row = lds4 + (size_t)(p * nsq + lane) * LS4;
-            f32x4 qd[8];
-            tower_cb_board_quads(m, n, qd);
-#pragma unroll
-            for (int k = 0; k < 4; k++) row[k] = qd[k];
-            const f32x4 lc[4] = {qd[4], qd[5], qd[6], qd[7]};
-            conv_last_chunk_store(row + 4, lc, T.cb_last_t);
-        }
-        tower_cb_table(ws, fcd, n, p, T.F >> 2, (const f32x4*)T.cplane_sums, (const f32x4*)T.b[0], pb4);
+#pragma unroll 1
+        for (int ch = lane; ch < F; ch += 64)
+            tower_cb_layer0<NB, F, true>(ws, fcd, m, T.cplane_sums, T.b[0], T.w0_rows, ch, [&](int o, float y) { put(p, o, ch, y); });
     };
+    // a wave's positions are requested two at a time (C2: 16 positions, 8 waves — one memory round trip instead of two)
     for (int p = wave; p < npos; p += 2 * NWAVES) {
         const int p1 = p + NWAVES;
         const WRaw r0 = ws_load_raw(states + (size_t)(pos0 + p) * geo.bytes, geo);
@@ -69,49 +66,19 @@ __device__ __forceinline__ void tower_stage_states_cb(f32x4* lds4, f32x4* pb4, c
         if (p1 < npos) stage_one(p1, r1);
     }
 }
-// The same for k_tower_sq, straight into the square-tile image (conv_mainloop_sq): the 32 board-plane channels of square sq of
-// position p in the first 8 slots of cell (p, sq); PB behind the image.  The positions a ragged workgroup lacks get zero planes
-// (their columns are computed and never stored; what they read must be finite).
-template <int NWAVES, int CH>
-__device__ __forceinline__ void tower_stage_states_cb_sq(f32x4* lds4, f32x4* pb4, const uint8_t* states, int pos0, int npos,
-                                                         const TowerParams& T) {
-    constexpr int n = SQ_NB, nsq = n * n, PW = 16, PP4 = sq_image_pitch4<CH>(), CP4 = sq_image_cell4<CH>(), LAST_T = 3;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const Geom geo = make_geom(n);
-    auto stage_one = [&](int p, const WRaw& raw) {
-        WState ws;
-        ws_unpack(ws, raw, geo);
-        const float fcd = fcd_value(ws, geo);
-        const RowMask m = ws_row_mask(ws, geo);
-        if (lane < nsq) {
-            f32x4* cell = lds4 + p * PP4 + lane * CP4;
-            f32x4 qd[8];
-            tower_cb_board_quads(m, n, qd);
-#pragma unroll
-            for (int k = 0; k < 4; k++) cell[k] = qd[k];
-            const f32x4 lc[4] = {qd[4], qd[5], qd[6], qd[7]};
-            conv_last_chunk_store(cell + 4, lc, LAST_T);
-        }
-        tower_cb_table(ws, fcd, n, p, 4 * CH, (const f32x4*)T.cplane_sums, (const f32x4*)T.b[0], pb4);
-    };
-    for (int p = wave; p < npos; p += 2 * NWAVES) {
-        const int p1 = p + NWAVES;
-        const WRaw r0 = ws_load_raw(states + (size_t)(pos0 + p) * geo.bytes, geo);
-        const WRaw r1 = ws_load_raw(states + (size_t)(pos0 + (p1 < npos ? p1 : p)) * geo.bytes, geo);
-        stage_one(p, r0);
-        if (p1 < npos) stage_one(p1, r1);
-    }
-    for (int idx = threadIdx.x; idx < (PW - npos) * nsq * 8; idx += NWAVES * 64) {
-        const int c = idx >> 3;
-        lds4[(npos + c / nsq) * PP4 + (c % nsq) * CP4 + (idx & 7)] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
+// the same when layer 0 is the whole tower (no residual block): straight into `out`
+template <int NWAVES, int NB, int F>
+__device__ __forceinline__ void tower_layer0_to_out(const uint8_t* states, int pos0, int npos, const TowerParams& T, float* __restrict__ out) {
+    tower_stage_layer0<NWAVES, NB, F>(states, pos0, npos, T, [&](int p, int o, int ch, float y) {
+        out[tower_out_index(T.frag_out, pos0 + p, o, ch, NB * NB, F)] = y;
+    });
 }
 
 // FROM_STATES: `in` points at packed game states and the planes are encoded straight into the LDS image
 // (game_repr fused into the tower: the f32 planes never touch HBM).
-// CB (with FROM_STATES): layer 0 over the board planes only, the constant planes as the per-position bias PB
-// (tower_stage_states_cb) — CH0 = 2 then.
-template <int RTW, int NWAVES, int CH0, int CH, bool FROM_STATES, bool CB = false>
+// CB (with FROM_STATES): layer 0 is a sum of weight rows (tower_stage_layer0) written straight into the image layer 1 reads;
+// the MFMA loops start at layer 1 — CH0 = 0 and NB = the board size then.
+template <int RTW, int NWAVES, int CH0, int CH, bool FROM_STATES, bool CB = false, int NB = 0>
 __global__ __launch_bounds__(NWAVES * 64) void k_tower(const float* __restrict__ in, TowerParams T, float* __restrict__ out,
                                                        int B, int n, int PW, int CTW) {
     static_assert(!CB || FROM_STATES, "the constant-plane bias needs the packed states");
@@ -129,11 +96,18 @@ __global__ __launch_bounds__(NWAVES * 64) void k_tower(const float* __restrict__
     const int ch0 = ct * 16;
 
     // ---- stage the input planes (row pitch cin_pad + 4) ----
-    int Cpad = CB ? T.cb_cin_pad : T.cin_pad;
+    int Cpad = CB ? F : T.cin_pad;
     int LS4 = (Cpad + LDS_PAD16) >> 2;
-    f32x4* pb4 = lds4 + (size_t)(PW * nsq + 1) * LS4;  // CB: PB[position][class][F] behind the image and its zero row
-    if (CB) {
-        tower_stage_states_cb<NWAVES>(lds4, pb4, (const uint8_t*)in, pos0, npos, n, LS4, T);
+    if constexpr (CB) {  // layer 0's outputs, the image of layer 1 (row pitch F + 8)
+        static_assert(NB * NB > 0 && CH0 == 0, "layer 0 as a sum of rows: no main loop");
+        if (T.nlayers == 1) {  // no residual block: layer 0 is the tower's output
+            tower_layer0_to_out<NWAVES, NB, 16 * CH>((const uint8_t*)in, pos0, npos, T, out);
+            return;
+        }
+        const int LS = LS4 * 4;
+        tower_stage_layer0<NWAVES, NB, 16 * CH>((const uint8_t*)in, pos0, npos, T, [&](int p, int o, int ch, float y) {
+            lds[(p * (NB * NB) + o) * LS + ch] = y;
+        });
         for (int idx = tid; idx < LS4; idx += NWAVES * 64) lds4[rows * LS4 + idx] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     } else if (FROM_STATES) {
         const Geom geo = make_geom(n);
@@ -200,25 +174,26 @@ __global__ __launch_bounds__(NWAVES * 64) void k_tower(const float* __restrict__
     conv_tap_masks<RTW>(rows, n, nsq, rho0, vmask);
     if (short_group) vmask[RTW - 1] = 0;  // that tile belongs to the next row group
 
-    for (int layer = 0; layer < T.nlayers; layer++) {
-        const f32x4* wp = (const f32x4*)(CB && layer == 0 ? T.w0_board : T.w[layer]) + ((size_t)(ch0 + r16) * 4 + q);
-        const int last_t0 = CB ? T.cb_last_t : T.cin_last_t;
+    for (int layer = CB ? 1 : 0; layer < T.nlayers; layer++) {
+        const f32x4* wp = (const f32x4*)T.w[layer] + ((size_t)(ch0 + r16) * 4 + q);
         TG_STAMP(layer, 0);
         if (RTW > 1 && short_group) {
             f32x4 (&acs)[RTW - 1] = *reinterpret_cast<f32x4 (*)[RTW - 1]>(&acc[0]);
-            if (layer == 0) conv_mainloop<RTW - 1, CH0>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acs, last_t0);
-            else conv_mainloop<RTW - 1, CH>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acs);
+            if constexpr (!CB) {
+                if (layer == 0) conv_mainloop<RTW - 1, CH0>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acs, T.cin_last_t);
+            }
+            if (CB || layer > 0) conv_mainloop<RTW - 1, CH>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acs);
         } else {
-            if (layer == 0) conv_mainloop<RTW, CH0>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acc, last_t0);
-            else conv_mainloop<RTW, CH>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acc);
+            if constexpr (!CB) {
+                if (layer == 0) conv_mainloop<RTW, CH0>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acc, T.cin_last_t);
+            }
+            if (CB || layer > 0) conv_mainloop<RTW, CH>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho0, q, vmask, acc);
         }
         TG_STAMP(layer, 1);
         // ---- epilogue on the accumulators: lane holds out[row][ch0 + 4q .. 4q+3] ----
         const f32x4 bv = *(const f32x4*)&T.b[layer][ch0 + 4 * q];
 #pragma unroll
-        for (int j = 0; j < RTW; j++) {
-            acc[j] = relu4(acc[j] + ((CB && layer == 0) ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 >> 2) + q)] : bv));
-        }
+        for (int j = 0; j < RTW; j++) acc[j] = relu4(acc[j] + bv);
         if (layer + 1 == T.nlayers) {
 #pragma unroll
             for (int j = 0; j < RTW; j++)
@@ -319,13 +294,7 @@ __global__ __launch_bounds__(NRT * CTW * 64) void k_tower_split(const uint8_t* _
     const int rho = rt * 16 + r16;  // this lane's row (square) of the position; ≥ rows: padding of the last row tile
     unsigned* flag = T.split_flags + (size_t)p * SPLIT_FLAG_STRIDE;  // a 128-byte line per position: its 8 pollers contend with nobody else
 
-    // ---- layer 0's image: the board planes of position p, the per-class bias table behind it (as k_tower, CB) ----
-    int LS4 = (T.cb_cin_pad + LDS_PAD16) >> 2;
-    f32x4* pb4 = lds4 + (size_t)(nsq + 1) * LS4;
-    tower_stage_states_cb<NW>(lds4, pb4, states, p, 1, n, LS4, T);
-    for (int idx = tid; idx < LS4; idx += NW * 64) lds4[rows * LS4 + idx] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    __syncthreads();
-
+    int LS4 = (F + LDS_PAD16) >> 2;
     int vmask[1];
     conv_tap_masks<1>(rows, n, nsq, rho, vmask);
     f32x4 acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -333,31 +302,56 @@ __global__ __launch_bounds__(NRT * CTW * 64) void k_tower_split(const uint8_t* _
     const size_t wlane = (size_t)(ch0 + r16) * 4 + q;
     f32x4 wf[CH];  // the first tap's weights of the NEXT layer: requested before the wait for the siblings, there when it ends
     for (int layer = 0; layer < T.nlayers; layer++) {
-        const f32x4* wp = (const f32x4*)(layer == 0 ? T.w0_board : T.w[layer]) + wlane;
-        const f32x4 bv = *(const f32x4*)&T.b[layer][ch0 + 4 * q];
-        TG_STAMP(layer, 0);
-        if (layer == 0) {  // (cb_last_t = 3, one 32-channel chunk pair: the launcher checks)
-            f32x4 wf0[2];
-            conv_tile_first_weights<2>(wp, (size_t)F * 4, wf0);
-            conv_mainloop_tile<2, 3>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho, q, vmask[0], acc, wf0);
-        } else conv_mainloop_tile<CH>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho, q, vmask[0], acc, wf);
-        TG_STAMP(layer, 1);
-        const f32x4 v = relu4(acc + (layer == 0 ? pb4[tower_cb_index(rho, rows, n, nsq, F4, (ch0 >> 2) + q)] : bv));
-        if (layer + 1 == T.nlayers) {
-            if (rho < rows) {
-                if (T.frag_out) ((f32x4*)out)[((size_t)(p >> 4) * (nsq * CH) + rho * CH + (ch0 >> 4)) * 64 + (p & 15) * 4 + q] = v;
-                else *(f32x4*)&out[((size_t)p * nsq + rho) * F + ch0 + 4 * q] = v;
-            }
-            break;
-        }
-        // the block input of conv2's accumulator: this wave's own slice of the image conv1 has just read (k_tower's skip path)
-        f32x4 x0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        if ((layer & 1) == 1 && rho < rows) x0 = lds4[rho * LS4 + (ch0 >> 2) + q];
-        acc = x0;
         // two exchange buffers used in turn (`out` is written by the last layer only: in the FC's fragment order a position's output
         // lies across the rows of 15 others)
         float* xbuf = scratch + (size_t)(layer & 1) * TOWER_SPLIT_MAX_BATCH * nsq * F;
-        if (rho < rows) *(f32x4*)&xbuf[((size_t)p * nsq + rho) * F + ch0 + 4 * q] = v;
+        TG_STAMP(layer, 0);
+        if (layer == 0) {
+            // layer 0 is a sum of weight rows (tower_cb_layer0, the one function every tower calls; lanes are channels): wave 0 sums
+            // this workgroup's slice of 16·CTW channels of position p and stores it into the exchange buffer like every other
+            // layer's, or into `out` when it is the tower's output
+            const bool last = T.nlayers == 1;
+            if (wave == 0) {
+                static_assert(CTW * 16 <= 64, "the workgroup's channels in one pass");
+                const int ch = g * CTW * 16 + (lane & (CTW * 16 - 1));  // (the lanes beyond the slice repeat it and store nothing)
+                float* dst = last ? out + tower_out_index(T.frag_out, p, 0, ch, nsq, F) : xbuf + (size_t)p * nsq * F + ch;
+                const int ostep = last && T.frag_out ? CH * 256 : F;  // floats between two squares of a position in `out` / xbuf
+                auto put = [&](int o, float y) {
+                    if (lane < CTW * 16) dst[o * ostep] = y;
+                };
+                WState ws;
+                const Geom geo = make_geom(n);
+                ws_load(ws, states + (size_t)p * geo.bytes, geo);
+                const float fcd = fcd_value(ws, geo);
+                const RowMask m = ws_row_mask(ws, geo);
+                // (opaque to the compiler: this branch does not change from layer to layer, and it would compute every row address
+                // before the layer loop and keep a hundred registers of them through all layers)
+                const float *S = T.cplane_sums, *R = T.w0_rows;
+                asm volatile("" : "+s"(S), "+s"(R));
+                if (n == 5) tower_cb_layer0<5, F, false>(ws, fcd, m, S, T.b[0], R, ch, put);
+                else tower_cb_layer0<6, F, false>(ws, fcd, m, S, T.b[0], R, ch, put);
+            }
+            TG_STAMP(layer, 1);
+            if (last) break;
+        } else {
+            const f32x4* wp = (const f32x4*)T.w[layer] + wlane;
+            const f32x4 bv = *(const f32x4*)&T.b[layer][ch0 + 4 * q];
+            conv_mainloop_tile<CH>(lds4, wp, (size_t)F * 4, LS4, rows, n, rho, q, vmask[0], acc, wf);
+            TG_STAMP(layer, 1);
+            const f32x4 v = relu4(acc + bv);
+            if (layer + 1 == T.nlayers) {
+                if (rho < rows) {
+                    if (T.frag_out) ((f32x4*)out)[((size_t)(p >> 4) * (nsq * CH) + rho * CH + (ch0 >> 4)) * 64 + (p & 15) * 4 + q] = v;
+                    else *(f32x4*)&out[((size_t)p * nsq + rho) * F + ch0 + 4 * q] = v;
+                }
+                break;
+            }
+            // the block input of conv2's accumulator: this wave's own slice of the image conv1 has just read (k_tower's skip path)
+            f32x4 x0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            if ((layer & 1) == 1 && rho < rows) x0 = lds4[rho * LS4 + (ch0 >> 2) + q];
+            acc = x0;
+            if (rho < rows) *(f32x4*)&xbuf[((size_t)p * nsq + rho) * F + ch0 + 4 * q] = v;
+        }
         if (SAME_L2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __syncthreads();  // every wave's slice is in L2 (SAME_L2) / on its way and every wave has finished reading the image
@@ -387,7 +381,6 @@ __global__ __launch_bounds__(NRT * CTW * 64) void k_tower_split(const uint8_t* _
         // SAME_L2: DEVICE-scope loads (sc1) — past this CU's L1, which may hold the buffer's lines of two layers ago, to the L2 the siblings'
         // stores went to.  (`buffer_inv sc0` + plain loads was 5 % faster and passed every test, but a counter polled that way saw the
         // siblings' atomics only after a long delay: the L1 was being emptied by the weight stream, not by the invalidate.)
-        LS4 = (F + LDS_PAD16) >> 2;
         const f32x4* src = (const f32x4*)(xbuf + (size_t)p * nsq * F);
         const int total = nsq * F4;
         constexpr int UNR = 8;
@@ -427,15 +420,16 @@ __global__ __launch_bounds__(NRT * CTW * 64) void k_tower_split(const uint8_t* _
 // The fused tower for full batches: as k_tower, but from layer 1 on the resident image is the HALO image of
 // conv_mainloop.cuh (zero cells between board rows and between positions), so the 3×3 taps are immediates and the main
 // loop is nothing but ds_read_b128 / MFMA / one weight load per chunk.  Layer 0 (other pitch, once per launch) runs
-// the masked loop on the plain image and writes its output straight into halo cells.  From layer 1 on the squares
+// the masked loop on the plain image and writes its output straight into halo cells; with CB (the states entry) it is a
+// sum of weight rows (tower_stage_layer0) written straight into the halo cells, no plain image at all.  From layer 1 on the squares
 // are dealt to (row tile, lane) slots by T.slotmap (tower_halo_slotmap): a permutation of the GEMM's M dimension,
 // invisible in the results, that keeps every ds_read_b128 of the loop off its neighbours' banks.
 // Per-element arithmetic (taps, chunks, k-steps, bias, ReLU, skip) in k_tower's order → identical bits.
 // ------------------------------------------------------------------------------------------------
 // Staging of the input planes and layer 0 on the plain image (tile t = rows 16t … 16t + 15), shared by the full-batch towers
-// k_tower_halo and k_tower_sq: leaves this wave's layer-0 outputs (bias and ReLU applied) of rows rho0 + 16j, j < my_tiles, in acc
+// k_tower_halo and k_tower_sq where layer 0 is dense (planes entry, TG_NO_CONST_BIAS): leaves this wave's layer-0 outputs (bias and ReLU applied) of rows rho0 + 16j, j < my_tiles, in acc
 // and requests layer 1's first two chunks of weights into w0 / w1.  The caller synchronises before it overwrites the image.
-template <int RTW, int NWAVES, int CH0, int CH, int NB, bool FROM_STATES, bool CB>
+template <int RTW, int NWAVES, int CH0, int CH, int NB, bool FROM_STATES>
 __device__ __forceinline__ void tower_plain_layer0(const float* __restrict__ in, const TowerParams& T, f32x4* lds4, int PW, int pos0,
                                                    int npos, int CTW, uint32_t wlane, f32x4 (&acc)[RTW], int& rho0_out,
                                                    int& my_tiles_out, f32x4& w0, f32x4& w1) {
@@ -448,12 +442,9 @@ __device__ __forceinline__ void tower_plain_layer0(const float* __restrict__ in,
     const int ch0 = ct * 16;
 
     // ---- stage the input planes: plain image, row pitch cin_pad + 8 floats, one zero row behind it ----
-    const int Cpad = CB ? T.cb_cin_pad : T.cin_pad;
+    const int Cpad = T.cin_pad;
     const int LS4 = (Cpad + LDS_PAD16) >> 2;
-    f32x4* pb4 = lds4 + (size_t)(PW * nsq + 1) * LS4;  // CB: PB[position][class][F] behind the image and its zero row
-    if (CB) {
-        tower_stage_states_cb<NWAVES>(lds4, pb4, (const uint8_t*)in, pos0, npos, n, LS4, T);
-    } else if (FROM_STATES) {
+    if (FROM_STATES) {
         const Geom geo = make_geom(n);
         const uint8_t* states = (const uint8_t*)in;
         const int C = input_channels(n);
@@ -512,8 +503,8 @@ __device__ __forceinline__ void tower_plain_layer0(const float* __restrict__ in,
     int vmask[RTW];
     conv_tap_masks<RTW>(rows, n, nsq, rho0, vmask);
     if (short_group) vmask[RTW - 1] = 0;
-    const f32x4* wp = (const f32x4*)(CB ? T.w0_board : T.w[0]) + ((size_t)(ch0 + r16) * 4 + q);
-    const int last_t0 = CB ? T.cb_last_t : T.cin_last_t;
+    const f32x4* wp = (const f32x4*)T.w[0] + ((size_t)(ch0 + r16) * 4 + q);
+    const int last_t0 = T.cin_last_t;
     TG_STAMP(0, 0);
     if (RTW > 1 && short_group) {
         f32x4 (&acs)[RTW - 1] = *reinterpret_cast<f32x4 (*)[RTW - 1]>(&acc[0]);
@@ -526,7 +517,7 @@ __device__ __forceinline__ void tower_plain_layer0(const float* __restrict__ in,
     const f32x4 bv = *(const f32x4*)&T.b[0][ch0 + 4 * q];
 #pragma unroll
     for (int j = 0; j < RTW; j++) {
-        acc[j] = relu4(acc[j] + (CB ? pb4[tower_cb_index(rho0 + j * 16, rows, n, nsq, F >> 2, (ch0 >> 2) + q)] : bv));
+        acc[j] = relu4(acc[j] + bv);
     }
     rho0_out = rho0;
     my_tiles_out = my_tiles;
@@ -553,10 +544,40 @@ __global__ __launch_bounds__(NWAVES * 64) void k_tower_halo(const float* __restr
     f32x4 w0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, w1 = w0;                // the weight stream's two chunks in flight between layers
     f32x4 acc[RTW];
     int rho0, my_tiles;
-    tower_plain_layer0<RTW, NWAVES, CH0, CH, NB, FROM_STATES, CB>(in, T, lds4, PW, pos0, npos, CTW, wlane, acc, rho0, my_tiles, w0, w1);
+    if constexpr (CB) {
+        // ---- layer 0 as a sum of weight rows, straight into the halo image ----
+        static_assert(CH0 == 0, "layer 0 as a sum of rows: no main loop");
+        if (T.nlayers == 1) {  // no residual block: layer 0 is the tower's output
+            tower_layer0_to_out<NWAVES, NB, F>((const uint8_t*)in, pos0, npos, T, out);
+            return;
+        }
+        conv_halo_first_weights<CH>(T.w[1], wlane, w0, w1);  // in flight while layer 0 is summed
+        // row tiles dealt to the row groups as in k_tower
+        const int NRG = NWAVES / CTW, rg = wave / CTW;
+        const int ntiles = (PW * nsq + 15) >> 4;
+        const int tbase = ntiles / NRG, trem = ntiles - tbase * NRG;
+        my_tiles = tbase + (rg < trem ? 1 : 0);
+        rho0 = (rg * tbase + min(rg, trem)) * 16 + r16;
+        // the zero cells of the image (they are never written again), and the cells of the positions a ragged workgroup lacks (their
+        // slots are computed and never stored; what they read must be finite)
+        const int cells = LEAD + PW * PS + 1;  // + the spare cell of the idle slots
+        for (int idx = tid; idx < cells * P4; idx += NWAVES * 64) {
+            const int c = idx / P4 - LEAD;
+            const int o = c < 0 || c >= PW * PS ? n * RS : c % PS;  // offset inside the position block; rows of RS cells, then the zero row
+            if (o >= n * RS || o % RS == n || c / PS >= npos) lds4[idx] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+        tower_stage_layer0<NWAVES, NB, F>((const uint8_t*)in, pos0, npos, T, [&](int p, int o, int ch, float y) {
+            lds[(LEAD + p * PS + (o / n) * RS + o % n) * (P4 * 4) + ch] = y;
+        });
+#pragma unroll
+        for (int j = 0; j < RTW; j++) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        TG_STAMP(0, 0); TG_STAMP(0, 1); TG_STAMP(0, 2);  // (no main loop, no epilogue: layer 0 is part of the staging)
+        __syncthreads();
+        TG_STAMP(0, 3); TG_STAMP(0, 4); TG_STAMP(0, 5);
+    } else tower_plain_layer0<RTW, NWAVES, CH0, CH, NB, FROM_STATES>(in, T, lds4, PW, pos0, npos, CTW, wlane, acc, rho0, my_tiles, w0, w1);
     const bool short_group = my_tiles < RTW;
     const int tile0 = (rho0 - r16) >> 4;
-    {
+    if constexpr (!CB) {
         TG_STAMP(0, 2);
         __syncthreads();  // every wave has finished reading the input planes
         TG_STAMP(0, 3);
@@ -641,10 +662,9 @@ __global__ __launch_bounds__(NWAVES * 64) void k_tower_halo(const float* __restr
 // The fused tower of 5×5 boards with 64 filters at full batches (16 positions per workgroup) on the square-tile image of
 // conv_mainloop_sq — row tile = board square, tile column = position of the workgroup — whose main loop issues the MFMAs
 // of the on-board taps only: 169 of the 225 (square, tap) pairs.
-// Layer 0 with the constant planes as a bias (CB, the states entry) runs on the same image: the board planes are staged into the
-// first 8 slots of every cell (tower_stage_states_cb_sq), the loop runs 2 chunks per tap and the 3 real MFMAs of the last
-// one, a tile's border class — which row of PB its epilogue adds — is a constant, and its outputs take the write-back of
-// every other layer.  Without CB (planes entry, 80 input channels) layer 0 stays on the plain image as in k_tower_halo.
+// Layer 0 with the constant planes as a bias (CB, the states entry) is a sum of weight rows (tower_stage_layer0): the wave that
+// unpacks a position writes its 25 × 64 outputs straight into the position's cells, no main loop, no image of the planes.
+// Without CB (planes entry, 80 input channels) layer 0 stays on the plain image as in k_tower_halo.
 // Waves w = 4·rg + ct: channel tile ct, row group rg (its squares: sq_tile); waves w and w + 4 share a SIMD.
 // Per-element arithmetic in k_tower's order, minus additions of exact zeros → identical bits.
 // ------------------------------------------------------------------------------------------------
@@ -672,19 +692,6 @@ __device__ __forceinline__ void tower_sq_writeback(f32x4* cell4, f32x4 (&acc)[13
     }
 }
 
-// layer 0's epilogue on square tiles: + PB[position][border class of the tile's square][channels], ReLU (pbq = PB + this lane's
-// position and channel quad)
-template <int RG, int CH>
-__device__ __forceinline__ void tower_sq_cb_epilogue(const f32x4* pbq, f32x4 (&acc)[13]) {
-#pragma unroll
-    for (int j = 0; j < sq_tiles(RG); j++) {
-        constexpr int n = SQ_NB;
-        const int sq = sq_tile(RG, j), y = sq / n, x = sq % n;
-        const int cls = (y == 0 ? 0 : y == n - 1 ? 2 : 1) * 3 + (x == 0 ? 0 : x == n - 1 ? 2 : 1);  // tower_cb_index
-        acc[j] = relu4(acc[j] + pbq[cls * 4 * CH]);
-    }
-}
-
 template <int CH0, bool FROM_STATES, bool CB = false>
 __global__ __launch_bounds__(512) void k_tower_sq(const float* __restrict__ in, TowerParams T, float* __restrict__ out, int B) {
     static_assert(!CB || FROM_STATES, "the constant-plane bias needs the packed states");
@@ -706,45 +713,30 @@ __global__ __launch_bounds__(512) void k_tower_sq(const float* __restrict__ in, 
     int ad = r16 * PP4 + q;  // this lane's tile column is position r16
     const int turn = rg;     // waves w and w + 4 share a SIMD
     if constexpr (CB) {
-        // ---- layer 0 on square tiles ----
-        static_assert(CH0 == 2, "board planes: 32 channels");
-        f32x4* pb4 = lds4 + PW * PP4;  // PB[position][class][F] behind the image
-        tower_stage_states_cb_sq<NWAVES, CH>(lds4, pb4, (const uint8_t*)in, pos0, npos, T);
-        conv_halo_first_weights<CH0, CH>(T.w0_board, wlane, w0, w1);
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < RTW; j++) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        asm volatile("" : "+v"(ad));
-        TG_STAMP(0, 0);
-        const float* wnext = T.nlayers > 1 ? T.w[1] : T.w0_board;
-        if (rg == 0) conv_mainloop_sq<0, CH, CH0, 3>(lds4 + ad, T.w0_board, wnext, wlane, acc, turn, w0, w1);
-        else conv_mainloop_sq<1, CH, CH0, 3>(lds4 + ad, T.w0_board, wnext, wlane, acc, turn, w0, w1);
-        TG_STAMP(0, 1);
-        // (a missing position of a ragged workgroup has no row of PB: position 0's, finite, never stored)
-        const f32x4* pbq = pb4 + (r16 < npos ? r16 : 0) * 9 * 4 * CH + (ch0 >> 2) + q;
-        if (rg == 0) tower_sq_cb_epilogue<0, CH>(pbq, acc);
-        else tower_sq_cb_epilogue<1, CH>(pbq, acc);
+        // ---- layer 0 as a sum of weight rows, straight into the square-tile image ----
+        static_assert(CH0 == 0, "layer 0 as a sum of rows: no main loop");
         if (T.nlayers == 1) {  // no residual block: layer 0 is the tower's output
-            if (r16 < npos) {
-                int p = pos0 + r16;
-                asm volatile("" : "+v"(p));
-                if (rg == 0) tower_sq_store<0, CH>(acc, T, out, p, q, ct);
-                else tower_sq_store<1, CH>(acc, T, out, p, q, ct);
-            }
+            tower_layer0_to_out<NWAVES, NB, 16 * CH>((const uint8_t*)in, pos0, npos, T, out);
             return;
         }
-        TG_STAMP(0, 2);
-        __syncthreads();  // every wave has finished reading the board planes and PB
-        TG_STAMP(0, 3);
-        f32x4* cell4 = lds4 + ad + (ch0 >> 2);
-        if (rg == 0) tower_sq_writeback<0, CH>(cell4, acc, false);
-        else tower_sq_writeback<1, CH>(cell4, acc, false);
-        TG_STAMP(0, 4);
+        conv_halo_first_weights<CH>(T.w[1], wlane, w0, w1);  // in flight while layer 0 is summed
+        tower_stage_layer0<NWAVES, NB, 16 * CH>((const uint8_t*)in, pos0, npos, T, [&](int p, int o, int ch, float y) {
+            lds[(p * PP4 + o * CP4) * 4 + ch] = y;
+        });
+        // the positions a ragged workgroup lacks get zero cells (their columns are computed and never stored; what they read must be
+        // finite)
+        for (int idx = tid; idx < (PW - npos) * nsq * 4 * CH; idx += NWAVES * 64) {
+            const int c = idx / (4 * CH);
+            lds4[(npos + c / nsq) * PP4 + (c % nsq) * CP4 + idx % (4 * CH)] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+#pragma unroll
+        for (int j = 0; j < RTW; j++) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        TG_STAMP(0, 0); TG_STAMP(0, 1); TG_STAMP(0, 2);  // (no main loop, no epilogue: layer 0 is part of the staging)
         __syncthreads();
-        TG_STAMP(0, 5);
+        TG_STAMP(0, 3); TG_STAMP(0, 4); TG_STAMP(0, 5);
     } else {  // layer 0 on the plain image (tile = 16 consecutive rows), then the change of images
         int rho0, my_tiles;
-        tower_plain_layer0<RTW, NWAVES, CH0, CH, NB, FROM_STATES, CB>(in, T, lds4, PW, pos0, npos, CTW, wlane, acc, rho0, my_tiles, w0, w1);
+        tower_plain_layer0<RTW, NWAVES, CH0, CH, NB, FROM_STATES>(in, T, lds4, PW, pos0, npos, CTW, wlane, acc, rho0, my_tiles, w0, w1);
         if (T.nlayers == 1) {  // no residual block: layer 0 is the tower's output
 #pragma unroll
             for (int j = 0; j < RTW; j++) {
@@ -814,18 +806,17 @@ __global__ __launch_bounds__(512) void k_tower_sq(const float* __restrict__ in, 
     }
 }
 
-// bytes of the per-position bias table PB behind the layer-0 image (TowerParams.cb)
-static size_t tower_cb_table_bytes(int PW, int F) { return (size_t)PW * 9 * F * sizeof(float); }
-
-template <int RTW, int NWAVES, int CH0, int CH, bool FROM_STATES, bool CB = false>
+// (CB: layer 0 needs no image of its own — its sums go straight into the image of layer 1)
+template <int RTW, int NWAVES, int CH0, int CH, bool FROM_STATES, bool CB = false, int NB = 0>
 static hipError_t launch_tower_t(hipStream_t st, const float* in, const TowerParams& T, float* out, int B, int n, int PW, int CTW) {
     const size_t rows1 = (size_t)(PW * n * n + 1);
-    const size_t first = rows1 * ((CB ? T.cb_cin_pad : T.cin_pad) + LDS_PAD16) * sizeof(float) + (CB ? tower_cb_table_bytes(PW, T.F) : 0);
+    const size_t first = CB ? 0 : rows1 * (T.cin_pad + LDS_PAD16) * sizeof(float);
     const size_t later = rows1 * (T.F + LDS_PAD16) * sizeof(float);
     const size_t lds = first > later ? first : later;
+    if (CB && (n != NB || !T.w0_rows)) return hipErrorInvalidValue;
     static LdsAttr lds_attr;
-    if (hipError_t e = lds_attr.ensure((const void*)k_tower<RTW, NWAVES, CH0, CH, FROM_STATES, CB>, lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_tower<RTW, NWAVES, CH0, CH, FROM_STATES, CB>), dim3((B + PW - 1) / PW), dim3(NWAVES * 64), lds, st, in, T, out, B, n, PW, CTW);
+    if (hipError_t e = lds_attr.ensure((const void*)k_tower<RTW, NWAVES, CH0, CH, FROM_STATES, CB, NB>, lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_tower<RTW, NWAVES, CH0, CH, FROM_STATES, CB, NB>), dim3((B + PW - 1) / PW), dim3(NWAVES * 64), lds, st, in, T, out, B, n, PW, CTW);
     return hipGetLastError();
 }
 
@@ -879,10 +870,10 @@ void tower_halo_slotmap(int n, int pw, int ps, uint32_t* out) {
 template <int RTW, int NWAVES, int CH0, int CH, int NB, bool FROM_STATES, bool CB = false>
 static hipError_t launch_tower_halo_t(hipStream_t st, const float* in, const TowerParams& T, float* out, int B, int CTW) {
     const int PW = T.halo_pw;
-    const size_t plain = (size_t)(PW * NB * NB + 1) * ((CB ? T.cb_cin_pad : T.cin_pad) + LDS_PAD16) * sizeof(float) +
-                         (CB ? tower_cb_table_bytes(PW, 16 * CH) : 0);
+    const size_t plain = CB ? 0 : (size_t)(PW * NB * NB + 1) * (T.cin_pad + LDS_PAD16) * sizeof(float);
     const size_t halo = (size_t)(NB + 2 + PW * T.halo_ps + 1) * (16 * CH + 4) * sizeof(float);  // + the spare cell
     const size_t lds = plain > halo ? plain : halo;
+    if (CB && !T.w0_rows) return hipErrorInvalidValue;
     static LdsAttr lds_attr;
     if (hipError_t e = lds_attr.ensure((const void*)k_tower_halo<RTW, NWAVES, CH0, CH, NB, FROM_STATES, CB>, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((k_tower_halo<RTW, NWAVES, CH0, CH, NB, FROM_STATES, CB>), dim3((B + PW - 1) / PW), dim3(NWAVES * 64), lds, st, in, T, out, B, PW, CTW);
@@ -892,13 +883,11 @@ static hipError_t launch_tower_halo_t(hipStream_t st, const float* in, const Tow
 template <int CH0, bool FROM_STATES, bool CB = false>
 static hipError_t launch_tower_sq_t(hipStream_t st, const float* in, const TowerParams& T, float* out, int B) {
     constexpr int PW = 16, NB = SQ_NB, CH = 4;
-    const size_t plain = (size_t)(PW * NB * NB + 1) * ((CB ? T.cb_cin_pad : T.cin_pad) + LDS_PAD16) * sizeof(float) +
-                         (CB ? tower_cb_table_bytes(PW, 16 * CH) : 0);
+    const size_t plain = (size_t)(PW * NB * NB + 1) * (T.cin_pad + LDS_PAD16) * sizeof(float);
     const size_t image = (size_t)PW * sq_image_pitch4<CH>() * 16;  // 115 200 B
-    // CB: layer 0 runs on the square-tile image too, PB behind it (152 064 B); its loop is built for 32 board channels, 3 real MFMAs
-    // in the last chunk
-    if (CB && (T.cb_cin_pad != 32 || T.cb_last_t != 3)) return hipErrorInvalidValue;
-    const size_t lds = CB ? image + tower_cb_table_bytes(PW, 16 * CH) : plain > image ? plain : image;
+    // CB: layer 0's sums go straight into the square-tile image
+    if (CB && !T.w0_rows) return hipErrorInvalidValue;
+    const size_t lds = CB ? image : plain > image ? plain : image;
     static LdsAttr lds_attr;
     if (hipError_t e = lds_attr.ensure((const void*)k_tower_sq<CH0, FROM_STATES, CB>, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((k_tower_sq<CH0, FROM_STATES, CB>), dim3((B + PW - 1) / PW), dim3(512), lds, st, in, T, out, B);
@@ -916,10 +905,10 @@ template <bool FROM_STATES>
 static bool launch_tower_halo(hipStream_t st, const float* in, const TowerParams& T, float* out, int B, int n, hipError_t* err) {
     static const bool off = env_on("TG_NO_HALO_TOWER");
     if (off || !T.slotmap) return false;
-    if (FROM_STATES && T.cb) {  // layer 0 over the board planes, constant planes as a bias (CH0 = 2)
-        if (tower_square_tiles(n, T.F, B)) { *err = launch_tower_sq_t<2, FROM_STATES, FROM_STATES>(st, in, T, out, B); return true; }
-        if (n == 6 && T.F == 128 && B > 512) { *err = launch_tower_halo_t<9, 8, 2, 8, 6, FROM_STATES, FROM_STATES>(st, in, T, out, B, 8); return true; }
-        if (n == 5 && T.F == 128 && B > 1024) { *err = launch_tower_halo_t<13, 8, 2, 8, 5, FROM_STATES, FROM_STATES>(st, in, T, out, B, 8); return true; }
+    if (FROM_STATES && T.cb) {  // layer 0 as a sum of weight rows, constant planes as a bias (no layer-0 loop: CH0 = 0)
+        if (tower_square_tiles(n, T.F, B)) { *err = launch_tower_sq_t<0, FROM_STATES, FROM_STATES>(st, in, T, out, B); return true; }
+        if (n == 6 && T.F == 128 && B > 512) { *err = launch_tower_halo_t<9, 8, 0, 8, 6, FROM_STATES, FROM_STATES>(st, in, T, out, B, 8); return true; }
+        if (n == 5 && T.F == 128 && B > 1024) { *err = launch_tower_halo_t<13, 8, 0, 8, 5, FROM_STATES, FROM_STATES>(st, in, T, out, B, 8); return true; }
         return false;
     }
     if (tower_square_tiles(n, T.F, B) && T.cin_pad == 80) { *err = launch_tower_sq_t<5, FROM_STATES>(st, in, T, out, B); return true; }
@@ -966,9 +955,7 @@ static bool workgroups_round_robin_over_xcds() {
 template <int NRT, int CTW, int CH>
 static hipError_t launch_tower_split_t(hipStream_t st, const uint8_t* states, const TowerParams& T, float* out, float* scratch, int B, int n) {
     const int nsq = n * n, F = 16 * CH;
-    const size_t first = (size_t)(nsq + 1) * (T.cb_cin_pad + LDS_PAD16) * sizeof(float) + tower_cb_table_bytes(1, F);
-    const size_t later = (size_t)(nsq + 1) * (F + LDS_PAD16) * sizeof(float);
-    const size_t lds = first > later ? first : later;
+    const size_t lds = (size_t)(nsq + 1) * (F + LDS_PAD16) * sizeof(float);
     constexpr int G = CH / CTW;
     const dim3 grid((B + 7) / 8 * 8 * G), block(NRT * CTW * 64);
     static const bool agent_fences = env_on("TG_SPLIT_AGENT_FENCES");  // A/B: the exchange with agent-scope fences wherever the siblings sit (same bits)
@@ -990,7 +977,7 @@ static hipError_t launch_tower_split_t(hipStream_t st, const uint8_t* states, co
 static bool launch_tower_split(hipStream_t st, const uint8_t* states, const TowerParams& T, float* out, float* scratch, int B, int n,
                                hipError_t* err) {
     static const bool off = env_on("TG_NO_SPLIT_TOWER");
-    if (off || !scratch || !T.cb || T.cb_last_t != 3 || T.cb_cin_pad != 32 || !T.split_flags || B > TOWER_SPLIT_MAX_BATCH || (T.nlayers & 1) == 0)
+    if (off || !scratch || !T.cb || !T.w0_rows || !T.split_flags || B > TOWER_SPLIT_MAX_BATCH || (T.nlayers & 1) == 0)
         return false;
     if (n == 5 && T.F == 64) { *err = launch_tower_split_t<2, 1, 4>(st, states, T, out, scratch, B, n); return true; }  // G = 4
     if (T.F != 128) return false;
@@ -1004,7 +991,7 @@ static bool launch_tower_split(hipStream_t st, const uint8_t* states, const Towe
 
 // The fused tower: full batches on the halo / square-tile image, small batches of wide networks split by channel tile (states entry
 // with a scratch buffer), everything else on k_tower with the whole-position tilings.  FROM_STATES: `in` holds packed game states,
-// encoded in-kernel; with T.cb layer 0 runs over the board planes alone (identical bits for every batch size).
+// encoded in-kernel; with T.cb layer 0 is the sum of the set board planes' weight rows (identical bits for every batch size).
 template <bool FROM_STATES>
 static hipError_t launch_tower_impl(hipStream_t st, const float* in, const TowerParams& T, float* out, int B, int n, float* scratch) {
     hipError_t herr;
@@ -1015,7 +1002,7 @@ static hipError_t launch_tower_impl(hipStream_t st, const float* in, const Tower
         using Tl = decltype(t);
         constexpr int CH = Tl::F / 16, CH0 = Tl::N == 5 ? 5 : 6;  // layer 0 over the 80 / 96 channels of the input planes
         if constexpr (FROM_STATES)
-            if (T.cb) return launch_tower_t<Tl::RTW, Tl::NWAVES, 2, CH, true, true>(st, in, T, out, B, n, Tl::PW, Tl::CTW);
+            if (T.cb) return launch_tower_t<Tl::RTW, Tl::NWAVES, 0, CH, true, true, Tl::N>(st, in, T, out, B, n, Tl::PW, Tl::CTW);
         return launch_tower_t<Tl::RTW, Tl::NWAVES, CH0, CH, FROM_STATES>(st, in, T, out, B, n, Tl::PW, Tl::CTW);
     });
 }
